@@ -12,6 +12,10 @@ N = 1 (the default): the workload is BASELINE.json configs[2] (C3: 100 k contigs
 contamination) at FULL size - the largest single-GPU config - generated on the GPU; configs[1] (C2) is measured
 afterwards and rides along as the "c2" object of the same line.
 
+A plain run sets up, warms up, times the steps alone and prints the line; --full adds everything else listed below and
+in parse_args, and times the steps with the record loop's HIP events inside the timed region.  --dump-outputs DIR writes
+what the last timed step computed (dump_outputs).
+
 Prints ONE JSON line on rank 0 (see the repo prompt for the contract) with two extra objects:
   roofline     - the WHOLE step priced at SURVEY 8(d)'s (38 + 32 f) bytes per read pair over the step time and
                  the 8 TB/s peak; the record loop's kernel (the dominant one) under its own name, with its algorithmic
@@ -74,6 +78,14 @@ def parse_args():
     ap.add_argument('--in-flight', type=int, default=3,
                     help='library passes kept in flight (one HIP stream each) for the extra "overlapped" figure; '
                          '0 skips it.  The headline value is always measured with ONE pass at a time.')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline: per-kernel breakdown and record-loop events, the checks against '
+                         'the C oracle, CPU baselines, the second config, overlapped passes, stages, robustness, C4 / C5 on '
+                         'one GPU, the weak-scaling point, the one-GPU figure of the same shape at N > 1.  Without it a run '
+                         'sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed (edge table, coverage, counters) as '
+                         'DIR/<name>.npy in float64, at most 64 MB (a seeded sample of a longer array)')
     return ap.parse_args()
 
 
@@ -745,7 +757,35 @@ def reference_calibration():
         return None
 
 
-def measure_single(args, device, config, steps, warmup, copies, pairs=None, contigs=None, verify=True, **variant):
+DUMP_BYTES = 60_000_000        # --dump-outputs: under 64 MB in all
+
+
+def step_outputs(table, aligned, counters):
+    """What a caller of the timed path receives from one step: the edge table's columns (EdgeTable), the per-contig
+    coverage numerators and the counters, as numpy arrays."""
+    out = {'edge_' + k: getattr(table, k) for k in ('key', 'mask', 'n', 'sum_obs', 'sum_obs_sq', 'first_idx', 'offset',
+                                                    'obs_lo', 'obs_hi')}
+    out['aligned'] = aligned.cpu().numpy()
+    out['counters'] = np.asarray(counters, dtype=np.int64)
+    return out
+
+
+def dump_outputs(path, arrays, writers=1):
+    """DIR/<name>.npy in float64: the columns are integers, which float64 holds exactly below 2^53 (keys of up to
+    2 x 23 + 1 bits, counts and sums of observations stay far below).  An array longer than its share of DUMP_BYTES (split
+    among `writers` processes writing into DIR) is cut to a sample at positions drawn from a seed fixed by its length, so
+    that two builds with equal outputs write equal files."""
+    os.makedirs(path, exist_ok=True)
+    cap = max(1, DUMP_BYTES // 8 // max(1, len(arrays) * writers))
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.shape[0] > cap:
+            a = a[np.sort(np.random.default_rng(a.shape[0]).choice(a.shape[0], cap, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a.astype(np.float64))
+
+
+def measure_single(args, device, config, steps, warmup, copies, pairs=None, contigs=None, verify=True, dump=None,
+                   **variant):
     """One GPU, one library pass at a time, records resident: timed steps, per-kernel breakdown, full-size check.
     Returns (result dict, workload, runner)."""
     import torch
@@ -771,41 +811,23 @@ def measure_single(args, device, config, steps, warmup, copies, pairs=None, cont
         runner.step()
     torch.cuda.synchronize()
     runner.check_capacity()
-    # the streaming kernel is timed with HIP events inside the timed region, on every 4th launch: an event pair costs
-    # the stream ~3 us, i.e. ~5 % of a C2 step when every launch carries one
-    lib_h.besst_prof_sample_every(4 if steps >= 8 else 1)
-    lib_h.besst_prof_enable(RECORD_LOOP_SLOTS)
+    if args.full:
+        # the streaming kernel is timed with HIP events inside the timed region, on every 4th launch: an event pair costs
+        # the stream ~3 us, i.e. ~5 % of a C2 step when every launch carries one
+        lib_h.besst_prof_sample_every(4 if steps >= 8 else 1)
+        lib_h.besst_prof_enable(RECORD_LOOP_SLOTS)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
         runner.step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    prof = pipeline.prof_collect()
-    lib_h.besst_prof_enable(0)
-    lib_h.besst_prof_sample_every(1)
-    lib_h.besst_prof_enable(0xffffffff)
-    for _ in range(args.breakdown_steps):
-        runner.step()
-    torch.cuda.synchronize()
-    breakdown = {k: round(v[0] / max(1, args.breakdown_steps), 4) for k, v in pipeline.prof_collect().items()}
-    lib_h.besst_prof_enable(0)
+    if dump:
+        dump_outputs(dump, runner.outputs())
     n_tuples, n_rows = runner.sizes()
     f = n_tuples / float(n_pairs)
     step_s = elapsed / steps
     alg_step = n_pairs * (38.0 + 32.0 * f)               # 2 x 19 B of records + 16 B per tuple written and read
-    # the record loop's kernel - the dominant one of every config - under its own name, priced at ITS algorithmic bytes:
-    # stream_kernel reads tid, mtid, mapq, qlen of every record (11 B; the candidates' other columns are ordered_kernel's);
-    # the fused forms read all seven columns once (19 B) and write every tuple (16 B)
-    loop_kernel = next((k for k in RECORD_LOOP_KERNELS if k in prof), None)
-    cls_ms, cls_launches = prof.get(loop_kernel, (0.0, 0))
-    cls_avg_s = (cls_ms / max(1, cls_launches)) * 1e-3
-    own = n_rec * 11.0 if loop_kernel == 'stream_kernel' else n_rec * 19.0 + n_tuples * 16.0
-    own_pmc = pmc_step_traffic(config, n_rec, loop_kernel)
-    dominant = max(breakdown.items(), key=lambda kv: kv[1])[0] if breakdown else None
-    verified = None
-    if verify and not args.no_verify and not args.no_cpu_baseline:
-        verified = verify_full(runner, wl)
     res = {
         'value': n_pairs / step_s,
         'ms_per_step': step_s * 1e3,
@@ -820,20 +842,41 @@ def measure_single(args, device, config, steps, warmup, copies, pairs=None, cont
             'achieved': round(alg_step / step_s / 1e9, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
             'frac': round(alg_step / step_s / 1e9 / HBM_PEAK_GBS, 4),
             'traffic': pmc_step_traffic(config, n_rec),
-            'algorithmic_bytes_per_step': alg_step, 'bytes_per_pair': round(38.0 + 32.0 * f, 3),
-            'dominant_kernel': dominant,
-            'record_loop_kernel': {'name': loop_kernel, 'algorithmic_bytes_per_launch': own,
-                                   'bytes': '11 B/record' if loop_kernel == 'stream_kernel' else '19 B/record + 16 B/tuple',
-                                   'avg_launch_ms': round(cls_avg_s * 1e3, 4), 'launches_timed': int(cls_launches),
-                                   'GBps': round(own / cls_avg_s / 1e9, 1) if cls_avg_s > 0 else None,
-                                   'frac': round(own / cls_avg_s / 1e9 / HBM_PEAK_GBS, 4) if cls_avg_s > 0 else None,
-                                   'pmc_bytes_per_launch': own_pmc,
-                                   'pmc_GBps': round(own_pmc / cls_avg_s / 1e9, 1) if own_pmc and cls_avg_s > 0 else None}},
-        'kernel_ms': breakdown,
-        'verified_vs_c_oracle': verified,
+            'algorithmic_bytes_per_step': alg_step, 'bytes_per_pair': round(38.0 + 32.0 * f, 3)},
         'generate_s': round(gen_s, 2),
         'stage2_form': 'tuple by tuple (the runs overflowed)' if runner.gb.sort_flags else 'default',
     }
+    if not args.full:
+        return res, wl, runner
+    prof = pipeline.prof_collect()
+    lib_h.besst_prof_enable(0)
+    lib_h.besst_prof_sample_every(1)
+    lib_h.besst_prof_enable(0xffffffff)
+    for _ in range(args.breakdown_steps):
+        runner.step()
+    torch.cuda.synchronize()
+    breakdown = {k: round(v[0] / max(1, args.breakdown_steps), 4) for k, v in pipeline.prof_collect().items()}
+    lib_h.besst_prof_enable(0)
+    # the record loop's kernel - the dominant one of every config - under its own name, priced at ITS algorithmic bytes:
+    # stream_kernel reads tid, mtid, mapq, qlen of every record (11 B; the candidates' other columns are ordered_kernel's);
+    # the fused forms read all seven columns once (19 B) and write every tuple (16 B)
+    loop_kernel = next((k for k in RECORD_LOOP_KERNELS if k in prof), None)
+    cls_ms, cls_launches = prof.get(loop_kernel, (0.0, 0))
+    cls_avg_s = (cls_ms / max(1, cls_launches)) * 1e-3
+    own = n_rec * 11.0 if loop_kernel == 'stream_kernel' else n_rec * 19.0 + n_tuples * 16.0
+    own_pmc = pmc_step_traffic(config, n_rec, loop_kernel)
+    res['roofline']['dominant_kernel'] = max(breakdown.items(), key=lambda kv: kv[1])[0] if breakdown else None
+    res['roofline']['record_loop_kernel'] = {
+        'name': loop_kernel, 'algorithmic_bytes_per_launch': own,
+        'bytes': '11 B/record' if loop_kernel == 'stream_kernel' else '19 B/record + 16 B/tuple',
+        'avg_launch_ms': round(cls_avg_s * 1e3, 4), 'launches_timed': int(cls_launches),
+        'GBps': round(own / cls_avg_s / 1e9, 1) if cls_avg_s > 0 else None,
+        'frac': round(own / cls_avg_s / 1e9 / HBM_PEAK_GBS, 4) if cls_avg_s > 0 else None,
+        'pmc_bytes_per_launch': own_pmc,
+        'pmc_GBps': round(own_pmc / cls_avg_s / 1e9, 1) if own_pmc and cls_avg_s > 0 else None}
+    res['kernel_ms'] = breakdown
+    res['verified_vs_c_oracle'] = verify_full(runner, wl) if verify and not args.no_verify and not args.no_cpu_baseline \
+        else None
     return res, wl, runner
 
 
@@ -896,11 +939,12 @@ DTYPE = 'int32/int64 (fp64 for read_len truncation)'
 
 
 def main_single(args, device, result_fd):
-    """N = 1: the headline is BASELINE.json configs[2] (C3, the largest single-GPU config) at full size; configs[1]
-    (C2) rides along as a second object of the same line."""
+    """N = 1: the headline is BASELINE.json configs[2] (C3, the largest single-GPU config) at full size; with --full,
+    configs[1] (C2) rides along as a second object of the same line."""
     import torch
     copies = args.copies if args.copies is not None else (1 if args.config == 'C3' else 3)
-    res, wl, runner = measure_single(args, device, args.config, args.steps, args.warmup, copies, args.pairs, args.contigs)
+    res, wl, runner = measure_single(args, device, args.config, args.steps, args.warmup, copies, args.pairs, args.contigs,
+                                     dump=args.dump_outputs)
     out = {
         'metric': METRIC, 'value': res['value'], 'unit': 'read-pairs/s', 'n_gpus': 1, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': res['ms_per_step'], 'higher_is_better': True, 'scaling': 'weak',
@@ -909,8 +953,13 @@ def main_single(args, device, result_fd):
                    'link_tuples_per_pair': res['link_tuples_per_pair'], 'edge_rows': res['edge_rows'],
                    'parallelism': 'single GPU', 'generator': 'besst_amd.synth.simulate_library_device (torch ops on the '
                    'GPU, seeded), %.1f s' % res['generate_s']},
-        'roofline': res['roofline'], 'kernel_ms': res['kernel_ms'], 'verified_vs_c_oracle': res['verified_vs_c_oracle'],
+        'roofline': res['roofline'],
     }
+    if not args.full:
+        sys.stdout.flush()
+        os.write(result_fd, (json.dumps(out) + '\n').encode())
+        return
+    out['kernel_ms'], out['verified_vs_c_oracle'] = res['kernel_ms'], res['verified_vs_c_oracle']
     out['roofline']['measured_d2d_copy_GBps'] = round(measured_copy_bandwidth(device), 1)
     if args.in_flight > 1:
         out['overlapped'] = overlapped_throughput(runner, wl, device, args.in_flight, max(args.steps, 30))
@@ -1042,9 +1091,13 @@ def main():
         port = sock.getsockname()[1]
         sock.close()
         os.dup2(result_fd, 1)                                # the ranks route their own output
-        os.execv(sys.executable, [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node',
-                                  str(args.gpus), '--master-addr', '127.0.0.1', '--master-port', str(port),
-                                  os.path.abspath(__file__)] + sys.argv[1:])
+        # a child process, not exec: this process has initialised the GPU, and replacing the program of such a process
+        # can take the driver down
+        import subprocess
+        rc = subprocess.call([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node',
+                              str(args.gpus), '--master-addr', '127.0.0.1', '--master-port', str(port),
+                              os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(rc)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -1378,7 +1431,7 @@ def main_sharded(args, device, rank, world, backend_name, force_dist, result_fd)
     # orchestration with a group of one, timed on rank 0 before the timed region - weak-scaling efficiency is value(N) /
     # (N x this), not against the C3 line that `--gpus 1` prints
     same_shape = None
-    if world > 1:
+    if world > 1 and args.full:
         solo_groups = [dist.new_group([r]) for r in range(world)]      # (collective: every rank makes every group)
         if rank == 0:
             solo = [distributed.ShardedGraphBuild(device, wl, 0, 1, group=solo_groups[0],
@@ -1415,8 +1468,9 @@ def main_sharded(args, device, rank, world, backend_name, force_dist, result_fd)
     torch.cuda.synchronize()
     for job in jobs:
         job.check_capacity()
-    lib_h.besst_prof_sample_every(1)
-    lib_h.besst_prof_enable(RECORD_LOOP_SLOTS)
+    if args.full:
+        lib_h.besst_prof_sample_every(1)
+        lib_h.besst_prof_enable(RECORD_LOOP_SLOTS)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -1427,18 +1481,29 @@ def main_sharded(args, device, rank, world, backend_name, force_dist, result_fd)
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    pipeline.prof_collect()
-    lib_h.besst_prof_enable(0)
+    if args.full:
+        pipeline.prof_collect()
+        lib_h.besst_prof_enable(0)
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device='cpu' if backend_name == 'gloo' else device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-    lib_h.besst_prof_enable(0xffffffff)
-    for _ in range(args.breakdown_steps):
-        step()
-    torch.cuda.synchronize()
-    breakdown = {k: round(v[0] / max(1, args.breakdown_steps), 4) for k, v in pipeline.prof_collect().items()}
-    lib_h.besst_prof_enable(0)
+    if args.dump_outputs:
+        # every rank its own share of the edge rows (the owned keys) and its view of coverage and counters
+        arrays = {}
+        for li, job in enumerate(jobs):
+            b = job.backend
+            part = step_outputs(b.local_table(), b.aligned, b.counter_words[:8].cpu().numpy())
+            arrays.update(('lib%d_rank%d_%s' % (li + 1, rank, k), v) for k, v in part.items())
+        dump_outputs(args.dump_outputs, arrays, writers=world)
+    breakdown = None
+    if args.full:
+        lib_h.besst_prof_enable(0xffffffff)
+        for _ in range(args.breakdown_steps):
+            step()
+        torch.cuda.synchronize()
+        breakdown = {k: round(v[0] / max(1, args.breakdown_steps), 4) for k, v in pipeline.prof_collect().items()}
+        lib_h.besst_prof_enable(0)
     libs_out, n_tuples_total, checks = [], 0, []
     for li, (job, wl) in enumerate(zip(jobs, wls)):
         n_tuples, n_rows = job.sizes()
@@ -1451,7 +1516,7 @@ def main_sharded(args, device, rank, world, backend_name, force_dist, result_fd)
                  'record_path': 'fused' if b.gb.params.record_path else 'two-pass', 'node_bits': wl['node_bits'],
                  'link_tuples': n_tuples, 'edge_rows': n_rows,
                  'exchange_consistent': bool(emitted == n_tuples and not b.overflowed())}
-        if not args.no_verify and not args.no_cpu_baseline:
+        if args.full and not args.no_verify and not args.no_cpu_baseline:
             try:
                 entry['verified_vs_c_oracle'] = verify_sharded_vs_oracle(job, wl, rank, world, device, backend_name)
             except Exception as e:                       # noqa: BLE001 - the bench line must still be printed
@@ -1480,16 +1545,17 @@ def main_sharded(args, device, rank, world, backend_name, force_dist, result_fd)
                          'traffic_note': 'PMC passes (rocprofv3 --pmc) are taken per process on one GPU: profiles/ holds '
                                          'them for the single-GPU step; none was collected under torch.distributed.run',
                          'algorithmic_bytes_per_step': alg_step},
-            'kernel_ms': breakdown,
-            'verified_vs_c_oracle': ok if not (args.no_verify or args.no_cpu_baseline) else None,
             'rccl_ranks_seen': int(dist.get_world_size()), 'backend': backend_name, 'device_uuids': uuids,
             'distinct_devices': len(set(uuids)), 'slices': args.slices if world > 1 else 'whole stream',
             'single_gpu_same_shape': same_shape if world > 1 else {
                 'ms_per_step': round(step_s * 1e3, 4), 'value': total_pairs / step_s, 'unit': 'read-pairs/s',
                 'what': 'this line: one rank through the sharded orchestration (all-to-all to itself) - the N = 1 point of '
                         'the weak-scaling curve, the per-GPU shape of --gpus 2 / 4 / 8'},
-            'cpu_baseline': sharded_cpu_baseline(args, wls[0]),
         }
+        if args.full:
+            out['kernel_ms'] = breakdown
+            out['verified_vs_c_oracle'] = ok if not (args.no_verify or args.no_cpu_baseline) else None
+            out['cpu_baseline'] = sharded_cpu_baseline(args, wls[0])
         if from_bam is not None:
             out['from_bam'] = from_bam
             if isinstance(out.get('single_gpu_same_shape'), dict):
@@ -1641,6 +1707,11 @@ class SingleGpu(object):
 
     def sizes(self):
         return self.gb.read_sizes()
+
+    def outputs(self):
+        c = self.gb.read_counters()
+        return step_outputs(self.gb.fetch_table(), self.gb.aligned,
+                            [getattr(c, name) for name, _ in type(c)._fields_])
 
     def check_capacity(self):
         n, _ = self.gb.read_sizes()

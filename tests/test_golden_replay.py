@@ -16,7 +16,7 @@ import pytest
 from tests import golden_util as GU
 from tests.refharness import loader
 
-pytestmark = pytest.mark.skipif(not loader.available(), reason='reference checkout not present')
+needs_reference = pytest.mark.skipif(not loader.available(), reason='reference checkout not present')
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -29,6 +29,7 @@ def maker():
     return mod, loader.load()
 
 
+@needs_reference
 @pytest.mark.parametrize('name', GU.scenario_names())
 def test_reference_reproduces_committed_fixture(maker, name):
     mod, mods = maker

@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ['--pairs', '400000', '--contigs', '3000', '--steps', '5', '--warmup', '2', '--cpu-sample-records', '200000']
+FULL = SMALL + ['--full']          # the checks against the oracle, the CPU legs and the extra figures
 
 
 def _last_json_line(text):
@@ -21,7 +22,7 @@ def _last_json_line(text):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py')] + SMALL, cwd=REPO, capture_output=True,
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py')] + FULL, cwd=REPO, capture_output=True,
                          text=True, timeout=420)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json_line(out.stdout)
@@ -41,6 +42,40 @@ def test_single_gpu_line_has_the_contract_fields():
     assert abs(d['value'] - 400000 / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
 
 
+def test_plain_line_is_the_headline_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full the line carries the headline and nothing measured besides it; --dump-outputs writes the last timed
+    step's edge table, coverage and counters, which must be what the C oracle computes on the same seeded stream."""
+    import numpy as np
+    import torch
+    from besst_amd import workload
+    from oracle import c_oracle as CO
+    dump = str(tmp_path / 'out')
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py')] + SMALL + ['--dump-outputs', dump], cwd=REPO,
+                         capture_output=True, text=True, timeout=420)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json_line(out.stdout)
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'roofline'):
+        assert k in d, k
+    assert d['steps'] == 5 and d['warmup'] == 2 and d['config']['workload'].startswith('C3')
+    assert abs(d['value'] - 400000 / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
+    for k in ('cpu_baseline', 'verified_vs_c_oracle', 'kernel_ms', 'stages', 'overlapped', 'c2', 'robustness'):
+        assert k not in d, k
+    got = {f[:-4]: np.load(os.path.join(dump, f)) for f in os.listdir(dump)}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(os.path.getsize(os.path.join(dump, f)) for f in os.listdir(dump)) <= 64 << 20
+    wl = workload.make_device(torch.device('cuda', 0), 'C3', 0, pairs=400000, nc=3000)
+    keys, payload, aligned, ctr = CO.record_loop(wl['batch'], wl['table'], wl['lib'], wl['node_bits'])
+    rows = CO.edge_rows(keys, payload)
+    assert got['edge_key'].shape[0] == d['config']['edge_rows'] == rows['key'].shape[0]
+    link = (rows['key'] & np.uint64(1)) == 0
+    for k in ('key', 'n', 'first_idx', 'obs_lo', 'obs_hi'):
+        assert np.array_equal(got['edge_' + k], rows[k].astype(np.float64)), k
+    for k in ('sum_obs', 'sum_obs_sq'):
+        assert np.array_equal(got['edge_' + k][link], rows[k][link].astype(np.float64)), k
+    assert np.array_equal(got['aligned'], aligned.astype(np.float64))
+    assert np.array_equal(got['counters'], ctr.astype(np.float64))
+
+
 def test_two_ranks_over_gloo_on_one_gpu():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
@@ -48,7 +83,7 @@ def test_two_ranks_over_gloo_on_one_gpu():
     s.close()
     env = dict(os.environ, BESST_DIST_BACKEND='gloo')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
-           '127.0.0.1', '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '2'] + SMALL
+           '127.0.0.1', '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '2'] + FULL
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=420)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json_line(out.stdout)
@@ -79,7 +114,7 @@ def test_two_ranks_with_independent_slices():
     env = dict(os.environ, BESST_DIST_BACKEND='gloo')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
            '127.0.0.1', '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--slices',
-           'independent'] + SMALL
+           'independent'] + FULL
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=420)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json_line(out.stdout)
@@ -97,7 +132,7 @@ def test_two_ranks_from_one_bam_file_per_library():
     s.close()
     env = dict(os.environ, BESST_DIST_BACKEND='gloo')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
-           '127.0.0.1', '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--from-bam'] + SMALL
+           '127.0.0.1', '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--from-bam'] + FULL
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json_line(out.stdout)
@@ -144,22 +179,30 @@ def test_gpus_n_that_disagrees_with_the_launcher_is_refused():
     assert not [l for l in out.stdout.splitlines() if l.startswith('{')]
 
 
-def test_gpus_n_without_a_launcher_starts_its_own_ranks():
-    """The self-launch (one rank per requested GPU under torch.distributed.run); gloo so that both fit this box's one GPU."""
+def test_gpus_n_without_a_launcher_starts_its_own_ranks(tmp_path):
+    """The self-launch (one rank per requested GPU under torch.distributed.run); gloo so that both fit this box's one GPU.
+    With --dump-outputs every rank writes the edge rows it owns: together, every row of each library once."""
+    import numpy as np
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     env['BESST_DIST_BACKEND'] = 'gloo'
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2'] + SMALL, cwd=REPO, env=env,
-                         capture_output=True, text=True, timeout=420)
+    dump = str(tmp_path / 'out')
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2'] + FULL + ['--dump-outputs', dump],
+                         cwd=REPO, env=env, capture_output=True, text=True, timeout=420)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json_line(out.stdout)
     assert d['n_gpus'] == 2 and d['rccl_ranks_seen'] == 2 and d['verified_vs_c_oracle'] is True
     assert d['single_gpu_same_shape']['value'] > 0
+    assert sum(os.path.getsize(os.path.join(dump, f)) for f in os.listdir(dump)) <= 64 << 20
+    for li, lib in enumerate(d['config']['libraries']):
+        keys = [np.load(os.path.join(dump, 'lib%d_rank%d_edge_key.npy' % (li + 1, r))) for r in (0, 1)]
+        assert keys[0].shape[0] + keys[1].shape[0] == lib['edge_rows']
+        assert np.unique(np.concatenate(keys)).shape[0] == lib['edge_rows']
 
 
 def test_one_rank_of_the_c4_shape_is_the_first_point_of_the_curve():
     """--config C4 --gpus 1: the per-GPU shape of --gpus 2 / 4 / 8 through the same orchestration over RCCL with one rank."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'BESST_DIST_BACKEND')}
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--config', 'C4'] + SMALL, cwd=REPO,
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--config', 'C4'] + FULL, cwd=REPO,
                          env=env, capture_output=True, text=True, timeout=420)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json_line(out.stdout)

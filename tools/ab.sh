@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for spec in "$@"; do
     label="${spec%%:*}"; envs="${spec#*:}"
-    env ${envs} python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-stages --no-robustness --no-verify --also "" \
+    env ${envs} python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-stages --no-robustness --no-verify --also "" \
         > "gpurun_out/ab_${label}.json" 2> "gpurun_out/ab_${label}.err"
     python - "$label" <<'PY'
 import json, sys
