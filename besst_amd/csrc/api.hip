@@ -1721,19 +1721,28 @@ int besst_dev_score_edges_lognormal(void* stream, int64_t n_edges, const uint32_
                       flags && workspace && F0 && F1,
                   "dev_score_edges_lognormal: null pointer");
     BESST_REQUIRE(sigma > 0.0 && ln_sigma > 0.0 && x_max >= 1 && max_gap >= 0, "dev_score_edges_lognormal: parameters out of range");
-    // [ big_off | sd0 (unused by the caller: the conditional sigma is looked up with the gap) | sort scratch ]
+    // [ big_off | sort scratch | tail tables G0, G1 and the workspace that builds them | sd0 (unused by the caller: the
+    //   conditional sigma is looked up with the gap) ]
     const size_t head = align_up((size_t)n_edges * 8, 256);
-    BESST_REQUIRE(workspace_bytes >= 2 * head, "dev_score_edges_lognormal: workspace too small");
+    const size_t tails = lognormal_dev_tails_bytes(x_max);
+    BESST_REQUIRE(workspace_bytes >= 2 * head + tails, "dev_score_edges_lognormal: workspace too small");
     ScoreArgs a;
     a.row = row; a.swap = swap; a.len1 = len1; a.len2 = len2;
     a.row_n = row_n; a.row_sum = row_sum; a.row_offset = row_offset;
     a.obs_lo = obs_lo; a.obs_hi = obs_hi;
     a.mean = mean; a.sigma = sigma; a.read_len = read_len;
     a.n_edges = n_edges;
-    LogNormalArgs l{ln_mu, ln_sigma, x_max, F0, F1, max_gap};
-    // the kernel wants the sort scratch right behind the offsets: the sd0 column sits at the END of the workspace
-    auto* sd0 = reinterpret_cast<double*>(static_cast<char*>(workspace) + workspace_bytes - head);
-    return launch_score_lognormal(static_cast<hipStream_t>(stream), a, l, gap, sd0, ks_h, flags, workspace, workspace_bytes - head);
+    // the kernel wants the sort scratch right behind the offsets: the tail tables and the sd0 column sit at the END
+    char* const end = static_cast<char*>(workspace) + workspace_bytes;
+    auto* sd0 = reinterpret_cast<double*>(end - head);
+    const size_t tab = align_up((size_t)(x_max + 1) * 8, 256);
+    auto* G0 = reinterpret_cast<double*>(end - head - tails);
+    auto* G1 = reinterpret_cast<double*>(end - head - tails + tab);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_lognormal_tails(s, ln_mu, ln_sigma, x_max, G0, G1, end - head - tails + 2 * tab, tails - 2 * tab);
+    if (rc) return rc;
+    LogNormalArgs l{ln_mu, ln_sigma, x_max, F0, F1, max_gap, G0, G1};
+    return launch_score_lognormal(s, a, l, gap, sd0, ks_h, flags, workspace, workspace_bytes - head - tails);
 }
 
 size_t besst_dev_mate_bits_bytes(int64_t n_records) { return (size_t)(((n_records > 0 ? n_records : 0) + 7) / 8) + 16; }
@@ -2209,18 +2218,24 @@ int besst_ctx_score_edges_lognormal(besst_ctx* c, int64_t n_edges, const uint32_
     BESST_REQUIRE(x_max >= 1 && x_max < ((int64_t)1 << 31) && max_gap >= 0, "score_edges_lognormal: parameters out of range");
     int rc = use_device(c);
     if (rc) return rc;
-    if (!(c->ln_tables.p && c->ln_mu == ln_mu && c->ln_sigma == ln_sigma && c->ln_x_max == x_max)) {
+    // [ F0 | F1 | G0 | G1 ]: prefix tables of x_max + 1 entries, tail tables of lognormal_tail_entries
+    const size_t ne = (size_t)lognormal_tail_entries(ln_mu, x_max);
+    double* const F0 = c->ln_tables.p;
+    if (!(F0 && c->ln_mu == ln_mu && c->ln_sigma == ln_sigma && c->ln_x_max == x_max)) {
         c->ln_x_max = 0;
-        if ((rc = c->ln_tables.ensure(2 * (size_t)(x_max + 1)))) return rc;
+        if ((rc = c->ln_tables.ensure(2 * (size_t)(x_max + 1) + 2 * ne))) return rc;
+        double* const T = c->ln_tables.p;
         const size_t wsb = lognormal_tables_workspace_bytes(x_max);
         if ((rc = c->aux.ensure(wsb))) return rc;
-        if ((rc = launch_lognormal_tables(c->stream, ln_mu, ln_sigma, x_max, c->ln_tables.p, c->ln_tables.p + (x_max + 1),
-                                          c->aux.p, wsb)))
+        if ((rc = launch_lognormal_tables(c->stream, ln_mu, ln_sigma, x_max, T, T + (x_max + 1), c->aux.p, wsb))) return rc;
+        if ((rc = launch_lognormal_tails(c->stream, ln_mu, ln_sigma, x_max, T + 2 * (x_max + 1), T + 2 * (x_max + 1) + ne,
+                                         c->aux.p, wsb)))
             return rc;
         BESST_HIP_TRY(hipStreamSynchronize(c->stream));          // aux is laid out anew below
         c->ln_mu = ln_mu; c->ln_sigma = ln_sigma; c->ln_x_max = x_max;
     }
-    LogNormalArgs ln{ln_mu, ln_sigma, x_max, c->ln_tables.p, c->ln_tables.p + (x_max + 1), max_gap};
+    const double* const T = c->ln_tables.p;
+    LogNormalArgs ln{ln_mu, ln_sigma, x_max, T, T + (x_max + 1), max_gap, T + 2 * (x_max + 1), T + 2 * (x_max + 1) + ne};
     return ctx_score_impl(c, n_edges, row, swap, len1, len2, mean, sigma, read_len, &ln, gap, nullptr, ks_h, flags);
 }
 

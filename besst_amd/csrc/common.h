@@ -434,8 +434,18 @@ struct LogNormalArgs {
     const double* F0;          // x_max + 1 entries each (launch_lognormal_tables)
     const double* F1;
     int32_t max_gap;           // len(conditional_stddevs) - 1
+    const double* G0;          // lognormal_tail_entries(mu, x_max) entries each (launch_lognormal_tails)
+    const double* G1;
 };
-size_t lognormal_tables_workspace_bytes(int64_t x_max);
+size_t lognormal_tables_workspace_bytes(int64_t x_max);     // (for either table pair)
+// what besst_dev_score_edges_lognormal keeps at the end of its workspace for the tail tables: two tables of (at most)
+// x_max + 1 doubles, each rounded up to 256 bytes, and the workspace that builds them
+inline size_t lognormal_dev_tails_bytes(int64_t x_max) {
+    return 2 * align_up((size_t)(x_max + 1) * 8, 256) + lognormal_tables_workspace_bytes(x_max);
+}
+int64_t lognormal_tail_entries(double mu, int64_t x_max);
+int launch_lognormal_tails(hipStream_t s, double mu, double sigma, int64_t x_max, double* G0, double* G1, void* ws,
+                           size_t ws_bytes);
 int launch_lognormal_tables(hipStream_t s, double mu, double sigma, int64_t x_max, double* F0, double* F1, void* ws,
                             size_t ws_bytes);
 int launch_score_lognormal(hipStream_t s, const ScoreArgs& a, const LogNormalArgs& l, double* gap, double* sd0,

@@ -2,21 +2,31 @@
 // (CreateGraph.py:498-614).  One workgroup per scored edge:
 //   * thread 0: naive gap, ML gap (bisection on d + sigma^2 g'(d)/g(d) = mu - mean_obs) and the
 //     expected std-dev of the truncated/skewed spanning density.  These restate the un-vendored
-//     mathstats 0.2.6.5 routines from the publication (besst_amd/mathstats_compat.py, same
-//     expressions in the same order; parity unpinned, +-1 bp tolerance on the gap).
+//     mathstats 0.2.6.5 routines from the publication (besst_amd/mathstats_compat.py: the same closed form,
+//     with the device's erf / exp; parity with the package unpinned).  Asserted against mpmath
+//     (tests/test_gpu_score_hp.py): the gap is one the bisection reaches when only conditions within their
+//     fp64 error bound of the naive gap may go either way; sd0 within 4x the host's error, 1e-12 relative,
+//     or its fp64 error bound.
 //   * all threads: the link-dispersity statistic.  l1 = sorted(obs of first endpoint) - mean,
 //     l2 = sorted(max(obs2) - obs2) - mean (:582-594); the two lists are bitonic-sorted in LDS (global
 //     scratch for edges with more than 8192 links) and h = max |#{l1 <= x} - #{l2 <= x}| over the pooled
 //     points is found with fp64 upper-bound searches, so ties are decided exactly like Python's float
-//     comparisons.  The KS statistic is h / n; the host forms the score.
+//     comparisons: h == py_oracle.ks_h, asserted at every storage class.  The KS statistic is h / n (SURVEY.md
+//     App. C.2); the host forms the score.
 // Log-normal branch (skewed libraries, param.lognormal; CreateGraph.py:485-494,522-531,549-553): the gap is the integer d
 // maximising L(d) = sum_i log f(o_i + d) - n log g(d) over the raw observations of the edge (mathstats'
 // log_normal_param_est.GapEstimator, restated in besst_amd/mathstats_compat.py: coarse scan with stride 64, then the 129
 // gaps around the coarse optimum).  The workgroup evaluates the gaps of a scan side by side, a group of lanes per gap
 // over the observations held in LDS; log g(d) comes from prefix tables F0 / F1 of the log-normal pmf built once per
-// library (lognormal_tables).  The conditional sigma table of get_conditional_stddevs (:436-469) is one small kernel.
+// library (lognormal_tables) below the median and tail tables G0 / G1 above it (lognormal_tails), so that a segment far in
+// the upper tail keeps its relative precision (plain prefix sums lose 4e-5 in log g at 23.6 kb for a 3 kb library, enough to move the argmax).  The
+// gap is asserted to be one the scan reaches when likelihoods within 2^-44 of the sum of their terms' magnitudes may tie
+// (long-double reference with direct sums, tests/test_gpu_score_hp.py).  The conditional sigma table of
+// get_conditional_stddevs (:436-469) is one small kernel.
 // fp64 throughout, compiled with -ffp-contract=off.
 #include <math.h>
+
+#include <cmath>
 
 #include "common.h"
 
@@ -148,7 +158,10 @@ struct LogNormal {
     long long x_max;           // support 1 .. x_max
     const double* F0;          // F0[k] = sum_{x <= k} f(x), k = 0 .. x_max
     const double* F1;          // F1[k] = sum_{x <= k} x f(x)
+    const double* G0;          // G0[j] = sum_{x > K + j} f(x), j = 0 .. x_max - K (the upper tail)
+    const double* G1;          // G1[j] = sum_{x > K + j} x f(x)
     int32_t max_gap;           // len(conditional_stddevs) - 1 (CreateGraph.py:493,527-528)
+    long long split;           // K = round(exp(mu)) in 1 .. x_max (mathstats_compat._lognormal_split)
 };
 
 __device__ __forceinline__ double lognormal_pmf(double x, double mu, double sigma) {
@@ -156,20 +169,31 @@ __device__ __forceinline__ double lognormal_pmf(double x, double mu, double sigm
     return exp(-((lx - mu) * (lx - mu)) / (2.0 * sigma * sigma)) / (x * sigma * sqrt(2.0 * M_PI));
 }
 
-// sums of f and x f over the integers of [a, b] clipped to the support
+// sums of f and x f over the integers of [a, b] clipped to the support: prefix tables where b <= K, tail tables where
+// a > K, both (cut at K) in between - no segment is a difference of two numbers near the total mass
+// (mathstats_compat._lognormal_log_g)
 __device__ __forceinline__ void ln_segment(const LogNormal& ln, long long a, long long b, double& s0, double& s1) {
     a = a < 1 ? 1 : (a > ln.x_max + 1 ? ln.x_max + 1 : a);
     b = b < 0 ? 0 : (b > ln.x_max ? ln.x_max : b);
     if (b >= a) {
-        s0 = ln.F0[b] - ln.F0[a - 1];
-        s1 = ln.F1[b] - ln.F1[a - 1];
+        const long long K = ln.split;
+        if (a - 1 >= K) {
+            s0 = ln.G0[a - 1 - K] - ln.G0[b - K];
+            s1 = ln.G1[a - 1 - K] - ln.G1[b - K];
+        } else if (b <= K) {
+            s0 = ln.F0[b] - ln.F0[a - 1];
+            s1 = ln.F1[b] - ln.F1[a - 1];
+        } else {
+            s0 = (ln.F0[K] - ln.F0[a - 1]) + (ln.G0[0] - ln.G0[b - K]);
+            s1 = (ln.F1[K] - ln.F1[a - 1]) + (ln.G1[0] - ln.G1[b - K]);
+        }
     } else {
         s0 = 0.0;
         s1 = 0.0;
     }
 }
 
-// log g(d): the three linear pieces of the placement weight against the prefix tables (mathstats_compat._lognormal_log_g)
+// log g(d): the three linear pieces of the placement weight against the tables (mathstats_compat._lognormal_log_g)
 __device__ double ln_log_g(const LogNormal& ln, long long d, long long c_min, long long c_max, long long r) {
     double s0, s1;
     ln_segment(ln, d + 2 * r, d + c_min + r - 1, s0, s1);                 // w = x - d - 2r + 1
@@ -511,9 +535,10 @@ int launch_score_impl(hipStream_t s, const ScoreArgs& a, const LogNormal& ln, do
     return BESST_OK;
 }
 
-// ---- prefix tables of the pmf: F0[k] = sum_{x <= k} f(x), F1[k] = sum_{x <= k} x f(x), k = 0 .. x_max ------------------
-// (mathstats_compat._lognormal_tables).  Three launches: sums per 2048-value tile, one workgroup scans the tile sums, every
-// tile writes its prefixes.  The tile and scan orders are fixed, so the tables are the same bits on every call.
+// ---- tables of the pmf (mathstats_compat._lognormal_tables / _lognormal_tail_tables): prefix sums F0[k] = sum_{x <= k} f(x),
+// F1[k] = sum_{x <= k} x f(x), k = 0 .. x_max; tail sums G0[j] = sum_{x > K + j} f(x), G1[j] = sum_{x > K + j} x f(x),
+// j = 0 .. x_max - K.  Per table pair three launches: sums per 2048-value tile, one workgroup scans the tile sums, every
+// tile writes its running sums.  The tile and scan orders are fixed, so the tables are the same bits on every call.
 constexpr int kLnThreads = 256, kLnPer = 8, kLnTile = kLnThreads * kLnPer;
 
 __device__ __forceinline__ void block_scan2(double& a, double& b, double* s_a, double* s_b, double& tot_a, double& tot_b) {
@@ -543,18 +568,21 @@ __device__ __forceinline__ void block_scan2(double& a, double& b, double* s_a, d
     __syncthreads();
 }
 
+// Running sums over the values x = x0 + i * step, i = 0 .. count - 1, the sum up to x written to F[x + shift] (prefix
+// tables: x0 = 1, step +1, shift 0, and F[0] = 0; tail tables: x0 = x_max, step -1, shift -1 - K).
 template <bool kWrite>
-__global__ __launch_bounds__(kLnThreads) void ln_tile_kernel(double mu, double sigma, long long x_max, double* __restrict__ tile0,
+__global__ __launch_bounds__(kLnThreads) void ln_tile_kernel(double mu, double sigma, long long x0, long long step, long long count,
+                                                             long long shift, double* __restrict__ tile0,
                                                              double* __restrict__ tile1, double* __restrict__ F0,
                                                              double* __restrict__ F1) {
     __shared__ double s_a[kLnThreads / 64], s_b[kLnThreads / 64];
-    const long long first = (long long)blockIdx.x * kLnTile + (long long)threadIdx.x * kLnPer + 1;   // x of this thread's first value
+    const long long first = (long long)blockIdx.x * kLnTile + (long long)threadIdx.x * kLnPer;   // i of this thread's first value
     double f[kLnPer];
     double a = 0.0, b = 0.0;
 #pragma unroll
     for (int k = 0; k < kLnPer; ++k) {
-        const long long x = first + k;
-        f[k] = x <= x_max ? lognormal_pmf((double)x, mu, sigma) : 0.0;
+        const long long x = x0 + (first + k) * step;
+        f[k] = first + k < count ? lognormal_pmf((double)x, mu, sigma) : 0.0;
         a += f[k];
         b += f[k] * (double)x;
     }
@@ -566,13 +594,13 @@ __global__ __launch_bounds__(kLnThreads) void ln_tile_kernel(double mu, double s
     }
     // (a, b) = sums of the threads in front of this one; the tile offsets were scanned exclusively in place
     double ra = tile0[blockIdx.x] + a, rb = tile1[blockIdx.x] + b;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { F0[0] = 0.0; F1[0] = 0.0; }
+    if (step > 0 && blockIdx.x == 0 && threadIdx.x == 0) { F0[0] = 0.0; F1[0] = 0.0; }
 #pragma unroll
     for (int k = 0; k < kLnPer; ++k) {
-        const long long x = first + k;
+        const long long x = x0 + (first + k) * step;
         ra += f[k];
         rb += f[k] * (double)x;
-        if (x <= x_max) { F0[x] = ra; F1[x] = rb; }
+        if (first + k < count) { F0[x + shift] = ra; F1[x + shift] = rb; }
     }
 }
 
@@ -625,11 +653,19 @@ int launch_score(hipStream_t s, const ScoreArgs& a, double* gap, double* sd0, in
     return launch_score_impl<false>(s, a, LogNormal{}, gap, sd0, ks_h, flags, ws);
 }
 
+// K = round(exp(mu)) inside 1 .. x_max, as mathstats_compat._lognormal_split (the host's libm: the same K as the host's)
+static long long lognormal_split(double mu, long long x_max) {
+    const long long k = (long long)std::floor(std::exp(mu) + 0.5);
+    return k < 1 ? 1 : (k > x_max ? x_max : k);
+}
+
+int64_t lognormal_tail_entries(double mu, int64_t x_max) { return x_max - lognormal_split(mu, (long long)x_max) + 1; }
+
 int launch_score_lognormal(hipStream_t s, const ScoreArgs& a, const LogNormalArgs& l, double* gap, double* sd0, int32_t* ks_h,
                            uint8_t* flags, void* ws, size_t ws_bytes) {
     (void)ws_bytes;
-    BESST_REQUIRE(l.sigma > 0.0 && l.x_max >= 1 && l.F0 && l.F1, "score: log-normal tables missing");
-    LogNormal ln{l.mu, l.sigma, (long long)l.x_max, l.F0, l.F1, l.max_gap};
+    BESST_REQUIRE(l.sigma > 0.0 && l.x_max >= 1 && l.F0 && l.F1 && l.G0 && l.G1, "score: log-normal tables missing");
+    LogNormal ln{l.mu, l.sigma, (long long)l.x_max, l.F0, l.F1, l.G0, l.G1, l.max_gap, lognormal_split(l.mu, (long long)l.x_max)};
     return launch_score_impl<true>(s, a, ln, gap, sd0, ks_h, flags, ws);
 }
 
@@ -647,11 +683,34 @@ int launch_lognormal_tables(hipStream_t s, double mu, double sigma, int64_t x_ma
     auto* tile0 = reinterpret_cast<double*>(ws);
     auto* tile1 = reinterpret_cast<double*>(static_cast<char*>(ws) + align_up((size_t)tiles * 8, 256));
     ProfScope ps(s, kProfScore);
-    hipLaunchKernelGGL((ln_tile_kernel<false>), dim3((uint32_t)tiles), dim3(kLnThreads), 0, s, mu, sigma, (long long)x_max,
-                       tile0, tile1, F0, F1);
+    hipLaunchKernelGGL((ln_tile_kernel<false>), dim3((uint32_t)tiles), dim3(kLnThreads), 0, s, mu, sigma, 1ll, 1ll,
+                       (long long)x_max, 0ll, tile0, tile1, F0, F1);
     hipLaunchKernelGGL(ln_tile_scan_kernel, dim3(1), dim3(kLnThreads), 0, s, tile0, tile1, tiles);
-    hipLaunchKernelGGL((ln_tile_kernel<true>), dim3((uint32_t)tiles), dim3(kLnThreads), 0, s, mu, sigma, (long long)x_max,
-                       tile0, tile1, F0, F1);
+    hipLaunchKernelGGL((ln_tile_kernel<true>), dim3((uint32_t)tiles), dim3(kLnThreads), 0, s, mu, sigma, 1ll, 1ll,
+                       (long long)x_max, 0ll, tile0, tile1, F0, F1);
+    BESST_HIP_TRY(hipGetLastError());
+    return BESST_OK;
+}
+
+int launch_lognormal_tails(hipStream_t s, double mu, double sigma, int64_t x_max, double* G0, double* G1, void* ws,
+                           size_t ws_bytes) {
+    BESST_REQUIRE(sigma > 0.0 && x_max >= 1 && x_max < ((int64_t)1 << 31), "lognormal_tails: parameters out of range");
+    BESST_REQUIRE(G0 && G1 && ws, "lognormal_tails: null pointer");
+    BESST_REQUIRE(ws_bytes >= lognormal_tables_workspace_bytes(x_max), "lognormal_tails: workspace too small");
+    const long long K = lognormal_split(mu, (long long)x_max), count = (long long)x_max - K;     // x = x_max down to K + 1
+    ProfScope ps(s, kProfScore);
+    BESST_HIP_TRY(hipMemsetAsync(G0 + count, 0, 8, s));                           // G[x_max - K] = 0
+    BESST_HIP_TRY(hipMemsetAsync(G1 + count, 0, 8, s));
+    if (count > 0) {
+        const long long tiles = (count + kLnTile - 1) / kLnTile;
+        auto* tile0 = reinterpret_cast<double*>(ws);
+        auto* tile1 = reinterpret_cast<double*>(static_cast<char*>(ws) + align_up((size_t)tiles * 8, 256));
+        hipLaunchKernelGGL((ln_tile_kernel<false>), dim3((uint32_t)tiles), dim3(kLnThreads), 0, s, mu, sigma, (long long)x_max,
+                           -1ll, count, -1 - K, tile0, tile1, G0, G1);
+        hipLaunchKernelGGL(ln_tile_scan_kernel, dim3(1), dim3(kLnThreads), 0, s, tile0, tile1, tiles);
+        hipLaunchKernelGGL((ln_tile_kernel<true>), dim3((uint32_t)tiles), dim3(kLnThreads), 0, s, mu, sigma, (long long)x_max,
+                           -1ll, count, -1 - K, tile0, tile1, G0, G1);
+    }
     BESST_HIP_TRY(hipGetLastError());
     return BESST_OK;
 }

@@ -32,8 +32,15 @@ Bioinformatics 28(17):2215, 2012) as summarised in SURVEY.md Appendix C.1:
 to unit width and returns the rounded midpoint; ``tr_sk_std_dev`` is the standard
 deviation of x under the density w(x) phi(x) / g(d).
 
-The device kernels (besst_amd/csrc/score.hip) and the C oracle (oracle/besst_oracle.c)
-implement the same expressions in the same evaluation order.
+The device kernels (besst_amd/csrc/score.hip) and the C oracle (oracle/besst_oracle.c) implement the same closed
+form, but with other erf / exp / log and, on the device, other summation orders, so the last bits differ.  What is
+asserted instead (tests/test_score_hp.py on the host, tests/test_gpu_score_hp.py on the device, against the
+high-precision references of oracle/score_hp.py): the gap of either is one the bisection can reach when every
+condition within 16x its fp64 error bound of the naive gap may go either way (a near tie; exact otherwise); sigma
+within its fp64 error bound of the mpmath value, and the device's error at most 4x the host's or 1e-12 relative
+wherever that bound is smaller; the log-normal gap one the scan can reach when likelihoods within 2^-44 of the sum of
+their terms' magnitudes may tie; the gap-table entries round like the mpmath condition except within its error bound of
+a rounding boundary.
 """
 import math
 
@@ -179,7 +186,8 @@ def PreCalcMLvaluesOfdLongContigs(mean, sigma, read_length, ctx=None):
     ctx: a besst_amd.device.GraphContext - the ML condition of every gap of the range is then evaluated by the
     device (besst_ctx_gap_condition_table, one thread per gap) and only the rounding and the inversion of the map
     stay on the host; without it everything runs here.  Both give the same table up to the last-bit differences of
-    the device's erf / exp at a rounding boundary (tests/test_gpu_score_numeric.py).
+    the device's erf / exp at a rounding boundary: an entry rounds differently from the mpmath condition only where that
+    lies within its fp64 error bound of k + 1/2 (tests/test_gpu_score_numeric.py, tests/test_gpu_score_hp.py).
     """
     big = 10.0 * (mean + 4 * sigma) + 10.0 * read_length
     d_upper = int(mean + 2 * sigma - 2 * read_length)
@@ -208,26 +216,54 @@ def PreCalcMLvaluesOfdLongContigs(mean, sigma, read_length, ctx=None):
 # (the placement weight of an observation does not depend on d).  Unlike the normal case L depends on every
 # observation, not only on their mean.  The estimate is the integer d maximising L over all gaps that keep every
 # x_i inside the support [1, exp(mu + 6 sigma)], found by a coarse scan (stride 64) and an exhaustive scan of the
-# 129 gaps around the coarse optimum.
+# 129 gaps around the coarse optimum.  g(d) comes from prefix tables of the pmf below its median and tail tables above it
+# (_lognormal_tail_tables): no segment sum is a difference of two numbers near the total mass, so log g keeps ~1e-13 at
+# every gap up to the end of the support.
 # ---------------------------------------------------------------------------------------------------------------
 def lognormal_support(mu, sigma):
     """x_max: the pmf lives on the integers 1 .. x_max."""
     return int(min(math.exp(mu + 6.0 * sigma), 4.0e6))
 
 
+def _lognormal_split(mu, x_max):
+    """K, where segment sums change from the prefix to the tail tables: the median exp(mu), rounded, inside 1 .. x_max."""
+    return min(max(1, int(math.floor(math.exp(mu) + 0.5))), x_max)
+
+
+def _lognormal_pmf(mu, sigma, x_max):
+    import numpy as np
+    x = np.arange(1, x_max + 1, dtype=np.float64)
+    lx = np.log(x)
+    return x, np.exp(-((lx - mu) ** 2) / (2.0 * sigma * sigma)) / (x * sigma * math.sqrt(2.0 * math.pi))
+
+
 def _lognormal_tables(mu, sigma):
     import numpy as np
     x_max = lognormal_support(mu, sigma)
-    x = np.arange(1, x_max + 1, dtype=np.float64)
-    lx = np.log(x)
-    f = np.exp(-((lx - mu) ** 2) / (2.0 * sigma * sigma)) / (x * sigma * math.sqrt(2.0 * math.pi))
+    x, f = _lognormal_pmf(mu, sigma, x_max)
     F0 = np.concatenate(([0.0], np.cumsum(f)))              # F0[k] = sum_{x <= k} f(x)
     F1 = np.concatenate(([0.0], np.cumsum(f * x)))
     return x_max, F0, F1
 
 
-def _lognormal_log_g(d, x_max, F0, F1, c_min, c_max, r):
-    """log g(d) for an array of integer gaps d (three linear pieces of w, prefix sums of f and x f)."""
+def _lognormal_tail_tables(mu, sigma):
+    """(K, G0, G1): G0[j] = sum_{x > K + j} f(x), G1[j] = sum_{x > K + j} x f(x) for j = 0 .. x_max - K, accumulated from
+    x_max downward (K = _lognormal_split).  A segment of the upper tail is then a difference of two small numbers: as a
+    difference of prefix sums it is one of two numbers near the total mass and loses ~eps / (mass of the segment), 4e-5 in
+    log g at 23.6 kb for a 3 kb library (tests/test_score_hp.py), enough to move the argmax of the scan."""
+    import numpy as np
+    x_max = lognormal_support(mu, sigma)
+    K = _lognormal_split(mu, x_max)
+    x, f = _lognormal_pmf(mu, sigma, x_max)
+    G0 = np.concatenate((np.cumsum(f[K:][::-1])[::-1], [0.0]))
+    G1 = np.concatenate((np.cumsum((f * x)[K:][::-1])[::-1], [0.0]))
+    return K, G0, G1
+
+
+def _lognormal_log_g(d, x_max, F0, F1, c_min, c_max, r, tails=None):
+    """log g(d) for an array of integer gaps d (three linear pieces of w).  The sums of f and x f over a segment [a, b]
+    come from the prefix tables F where b <= K, from the tail tables (tails = _lognormal_tail_tables(...)) where a > K,
+    and from both, cut at K, in between; tails None: prefix tables throughout."""
     import numpy as np
     d = np.asarray(d, dtype=np.int64)
 
@@ -237,7 +273,14 @@ def _lognormal_log_g(d, x_max, F0, F1, c_min, c_max, r):
         ok = b >= a
         a0 = np.where(ok, a, 1)
         b0 = np.where(ok, b, 0)
-        return np.where(ok, F0[b0] - F0[a0 - 1], 0.0), np.where(ok, F1[b0] - F1[a0 - 1], 0.0)
+        s0, s1 = F0[b0] - F0[a0 - 1], F1[b0] - F1[a0 - 1]
+        if tails is not None:
+            K, G0, G1 = tails
+            ja, jb = np.clip(a0 - 1 - K, 0, None), np.clip(b0 - K, 0, None)
+            upper, cut = a0 - 1 >= K, (a0 - 1 < K) & (b0 > K)
+            s0 = np.where(upper, G0[ja] - G0[jb], np.where(cut, (F0[K] - F0[a0 - 1]) + (G0[0] - G0[jb]), s0))
+            s1 = np.where(upper, G1[ja] - G1[jb], np.where(cut, (F1[K] - F1[a0 - 1]) + (G1[0] - G1[jb]), s1))
+        return np.where(ok, s0, 0.0), np.where(ok, s1, 0.0)
     s0, s1 = seg(d + 2 * r, d + c_min + r - 1)               # w = x - d - 2r + 1
     g = s1 - (d + 2 * r - 1) * s0
     s0, s1 = seg(d + c_min + r, d + c_max + r)               # w = c_min - r + 1
@@ -260,8 +303,8 @@ def lognormal_GapEstimator(mu, sigma, read_length, samples, c1_len, c2_len=None)
     key = (float(mu), float(sigma))
     if key not in _LN_CACHE:
         _LN_CACHE.clear()
-        _LN_CACHE[key] = _lognormal_tables(mu, sigma)
-    x_max, F0, F1 = _LN_CACHE[key]
+        _LN_CACHE[key] = _lognormal_tables(mu, sigma) + (_lognormal_tail_tables(mu, sigma),)
+    x_max, F0, F1, tails = _LN_CACHE[key]
     if c2_len is None:
         c2_len = 10 * x_max
     r = int(round(read_length))
@@ -278,7 +321,7 @@ def lognormal_GapEstimator(mu, sigma, read_length, samples, c1_len, c2_len=None)
             blk = ds[a:a + step]
             lx = np.log((obs[None, :] + blk[:, None]).astype(np.float64))
             out[a:a + step] = (-lx - ((lx - mu) ** 2) / (2.0 * sigma * sigma)).sum(axis=1)
-        lg = _lognormal_log_g(ds, x_max, F0, F1, c_min, c_max, r)
+        lg = _lognormal_log_g(ds, x_max, F0, F1, c_min, c_max, r, tails)
         with np.errstate(invalid='ignore'):
             return np.where(np.isfinite(lg), out - n * lg, -np.inf)      # no spanning fragment at this gap: never chosen
     coarse = np.arange(d_lo, d_hi + 1, 64, dtype=np.int64)

@@ -335,8 +335,12 @@ class DeviceGraphBuilder(object):
         big = np.where(npow > 8192, 2 * npow, 0)
         big_off = (np.cumsum(big) - big).astype(np.uint64)
         off_bytes = (m * 8 + 255) // 256 * 256
-        ws = torch.zeros(off_bytes + (int(big.sum()) * 4 + 256 + 255) // 256 * 256 + (off_bytes if lognormal is not None else 0),
-                         dtype=torch.uint8, device=dev)
+        extra = 0
+        if lognormal is not None:                            # sd0, the tail tables of the pmf and their build workspace
+            x_max = int(lognormal[2])
+            extra = off_bytes + 2 * (((x_max + 1) * 8 + 255) // 256 * 256) + \
+                int(self.lib.besst_dev_lognormal_tables_workspace_bytes(x_max))
+        ws = torch.zeros(off_bytes + (int(big.sum()) * 4 + 256 + 255) // 256 * 256 + extra, dtype=torch.uint8, device=dev)
         ws[:m * 8] = torch.from_numpy(big_off.view(np.uint8)).to(dev)
         d = [torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
              for a, dt in ((rows.view(np.int32), np.int32), (swap, np.uint8), (len1, np.int32), (len2, np.int32))]

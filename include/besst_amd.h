@@ -317,7 +317,7 @@ int besst_ctx_score_edges(besst_ctx* ctx, int64_t n_edges, const uint32_t* row, 
  * un-vendored, restated in besst_amd/mathstats_compat.py): the integer d maximising
  *     L(d) = sum_i log f(o_i + d) - n log g(d),   f = log-normal pmf on 1 .. x_max,   g(d) = sum_x w(x; d) f(x)
  * over the gaps that keep every o_i + d inside the support - coarse scan with stride 64, then the 129 gaps around the
- * coarse optimum - clamped to max_gap = len(conditional_stddevs) - 1 (:527-528).  The pmf's prefix tables are built on
+ * coarse optimum - clamped to max_gap = len(conditional_stddevs) - 1 (:527-528).  The pmf's prefix and tail tables are built on
  * the device at the first call and kept while (ln_mu, ln_sigma, x_max) stay the same.  x_max is passed in (the caller's
  * int(min(exp(ln_mu + 6 ln_sigma), 4e6))) so that host and device agree on the support.  There is no sd0 output: the
  * caller indexes the conditional sigma table (besst_ctx_conditional_stddevs) with the gap (:549-553). */
@@ -569,8 +569,11 @@ int besst_dev_mate_bits(void* stream, int64_t n_records, const int32_t* tid, con
  *   besst_dev_lognormal_tables   F0[k] = sum_{x <= k} f(x), F1[k] = sum_{x <= k} x f(x) for k = 0 .. x_max (x_max + 1
  *                                doubles each), f the pmf of LogNormal(mu, sigma) on the integers; workspace:
  *                                besst_dev_lognormal_tables_workspace_bytes(x_max)
- *   besst_dev_score_edges_lognormal   workspace as for besst_dev_score_edges plus one more [8 bytes x n_edges, rounded up
- *                                to 256] at its end */
+ *   besst_dev_score_edges_lognormal   workspace as for besst_dev_score_edges plus, at its end, 2 x [8 bytes x (x_max + 1),
+ *                                rounded up to 256] + besst_dev_lognormal_tables_workspace_bytes(x_max) (the tail sums
+ *                                of the pmf above its median, built there on every call: a segment of the upper tail
+ *                                is not taken as a difference of two prefix sums near the total mass) and one more
+ *                                [8 bytes x n_edges, rounded up to 256] */
 size_t besst_dev_lognormal_tables_workspace_bytes(int64_t x_max);
 int besst_dev_lognormal_tables(void* stream, double mu, double sigma, int64_t x_max, double* F0, double* F1,
                                void* workspace, size_t workspace_bytes);
