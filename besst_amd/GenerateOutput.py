@@ -1,11 +1,27 @@
-"""The four output helpers that the hot path calls from inside CreateGraph.PE.
+"""Output of the scaffolding result, and the four helpers that the hot path calls from inside CreateGraph.PE.
 
-Only the functions reached from the graph-construction path are provided (reference:
-GenerateOutput.py:47-85, called at CreateGraph.py:432,803,1012-1013).  They matter for parity because
-they DELETE the removed contigs from the caller's dicts.  FASTA/AGP/GFF writers of the scaffolding
-result are downstream of this path and stay with the reference.
+The helpers (reference: GenerateOutput.py:47-85, called at CreateGraph.py:432,803,1012-1013) matter for parity because
+they DELETE the removed contigs from the caller's dicts.
+
+``WriteToF`` / ``PrintOutput`` (reference :88-227) write ``Scaffolds-pass<n>.fa``, ``info-pass<n>.agp`` and
+``info-pass<n>.gff``.  The sequence work is done on the device (csrc/emit.hip): the contigs lie in a
+:class:`SequenceStore` in HBM for the whole run, ``seq_overlap_kernel`` finds the overlaps of the junctions that may
+merge, the host turns placements + overlaps into a piece table with numpy, and ``emit_kernel`` gathers the FASTA bytes
+(copy / reverse-complement / 'N' fill) in chunks that are copied back and written while the next chunk is produced.
+AGP and GFF are plain text from names, positions and gaps.  Like the rest of the package there is no CPU path: without
+the library or a GPU these calls raise :class:`besst_amd._lib.BesstDeviceError`.
 """
 from __future__ import print_function
+
+import ctypes as _C
+import os
+import time
+import warnings
+
+import numpy as np
+
+from . import _lib
+from ._lib import BesstDeviceError
 
 
 def _write_fasta(handle, name, sequence):
@@ -62,4 +78,430 @@ def ChangeToSmallContigs(Contigs, list_of_contigs, small_contigs):
     for cont_obj in list_of_contigs:
         del Contigs[cont_obj.name]
         small_contigs[cont_obj.name] = cont_obj
+    return ()
+
+
+# ---- the scaffolds themselves: FASTA / AGP / GFF (reference GenerateOutput.py:88-227) -----------------------------------
+MAX_CONTIG_OVERLAP_LIMIT = 4096          # include/besst_amd.h: BESST_MAX_CONTIG_OVERLAP
+EMIT_PAD = 32                            # include/besst_amd.h: BESST_EMIT_PAD
+PIECE_COPY, PIECE_REVCOMP, PIECE_FILL_N, PIECE_LITERAL = 0, 1, 2, 3
+MIN_MERGE_OVERLAP = 20                   # reference :140
+CHUNK_BYTES = 256 << 20                  # PrintOutput produces the FASTA in chunks of this size
+NO_ERROR = 0xFFFFFFFFFFFFFFFF
+last_timings = {}                        # PrintOutput's wall-time split of its latest call (seconds)
+
+
+def WriteToF(F, Contigs, list_of_contigs):
+    info_list = []
+    for cont_obj in list_of_contigs:
+        info_list.append((cont_obj.name, cont_obj.direction, cont_obj.position, cont_obj.length, cont_obj.sequence))
+        if cont_obj.position < 0:
+            print('Write to F: Position is negative!', cont_obj.position, cont_obj.name, cont_obj.direction)
+    F.append(info_list)
+    return F
+
+
+def pack_sequences(sequences):
+    """-> (pool uint8, offsets int64, lengths int32): the sequences end to end, one byte per base, as given."""
+    parts = []
+    for seq in sequences:
+        if isinstance(seq, str):
+            try:
+                seq = seq.encode('ascii')
+            except UnicodeEncodeError:
+                raise ValueError('contig sequences must be ASCII')
+        elif seq is None:
+            seq = b''
+        else:
+            seq = bytes(seq)
+            if seq.translate(None, _ASCII):
+                raise ValueError('contig sequences must be ASCII')
+        parts.append(seq)
+    lengths = np.fromiter((len(p) for p in parts), dtype=np.int64, count=len(parts))
+    if len(parts) and int(lengths.max()) >= 1 << 31:
+        raise ValueError('a contig of 2^31 bases or more')
+    offsets = np.zeros(len(parts), dtype=np.int64)
+    if len(parts) > 1:
+        np.cumsum(lengths[:-1], out=offsets[1:])
+    pool = np.frombuffer(b''.join(parts), dtype=np.uint8)
+    return pool, offsets, lengths.astype(np.int32)
+
+
+_ASCII = bytes(range(128))
+
+
+def _torch_device(device):
+    try:
+        import torch
+    except ImportError as exc:
+        raise BesstDeviceError('scaffold output needs torch for ROCm: %s' % exc)
+    _lib.load()
+    if not torch.cuda.is_available():
+        raise BesstDeviceError('scaffold output needs a GPU (besst_amd has no CPU fallback)')
+    return torch, torch.device('cuda', int(device))
+
+
+def _padded_upload(torch, dev, host_bytes):
+    """uint8 tensor with EMIT_PAD zero bytes on either side of the data -> (tensor, pointer of the data)."""
+    n = int(host_bytes.shape[0])
+    t = torch.zeros(n + 2 * EMIT_PAD, dtype=torch.uint8, device=dev)
+    if n:
+        with warnings.catch_warnings():                          # a read-only view of a bytes object: it is only read
+            warnings.simplefilter('ignore', UserWarning)
+            t[EMIT_PAD:EMIT_PAD + n].copy_(torch.from_numpy(host_bytes))
+    return t, t.data_ptr() + EMIT_PAD
+
+
+class SequenceStore(object):
+    """The contig sequences of a run in HBM: uploaded once, read by every pass's output (only placements change between
+    libraries).  One byte per base - case and IUPAC codes survive."""
+
+    def __init__(self, names, sequences, device=0):
+        names = list(names)
+        pool, self.offsets, self.lengths = pack_sequences(sequences)
+        if len(names) != len(self.offsets):
+            raise ValueError('need one name per sequence')
+        self.index = {name: i for i, name in enumerate(names)}
+        self.pool_bytes = int(pool.shape[0])
+        torch, dev = _torch_device(device)
+        self.device = dev
+        self._pool, self.pool_ptr = _padded_upload(torch, dev, pool)
+        self._off = torch.from_numpy(self.offsets).to(dev)
+        self._len = torch.from_numpy(self.lengths).to(dev)
+
+    @classmethod
+    def from_contigs(cls, Contigs, small_contigs, device=0):
+        objs = list(Contigs.values()) + list(small_contigs.values())
+        return cls([c.name for c in objs], [c.sequence for c in objs], device=device)
+
+    def __len__(self):
+        return len(self.offsets)
+
+    def byte_at(self, pool_offset):
+        return int(self._pool[EMIT_PAD + int(pool_offset)].item())
+
+    def close(self):
+        self._pool = self._off = self._len = None
+        self.pool_ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class ScaffoldLayout(object):
+    """Host side of PrintOutput: the scaffolds in output order (reversed(F), each sorted by position, :213-216), their
+    junctions, and - once the overlaps are known - the piece table of the FASTA file.  Pure numpy / Python; no device.
+
+    ``offsets`` / ``lengths``: where every sequence lies in the pool; ``index``: name -> row of those (None: the tuples
+    of F in output order are the rows)."""
+
+    def __init__(self, F, param, unique_id, offsets, lengths, index=None):
+        K = param.max_contig_overlap
+        if K < 0:
+            raise ValueError('max_contig_overlap must not be negative')
+        if K > MAX_CONTIG_OVERLAP_LIMIT:
+            raise ValueError('max_contig_overlap above %d is not supported' % MAX_CONTIG_OVERLAP_LIMIT)
+        self.max_overlap = int(K)
+        self.scaffolds = [sorted(scaf, key=lambda t: t[2]) for scaf in reversed(F)]
+        self.names = ['scaffold_' + str(k + 1) + '_uid_' + str(unique_id) for k in range(len(self.scaffolds))]
+        two_sigma = 2 * param.std_dev_ins_size
+        row, fwd, first, sep_n, fill, cand = [], [], [], [], [], []
+        for scaf in self.scaffolds:
+            prev = None
+            for t in scaf:
+                row.append(len(row) if index is None else index[t[0]])
+                fwd.append(bool(t[1]))
+                first.append(prev is None)
+                if prev is None:
+                    sep_n.append(False); fill.append(0); cand.append(False)
+                else:
+                    gap = t[2] - (prev[2] + prev[3])
+                    cand.append(bool(gap <= two_sigma))
+                    sep_n.append(bool(gap <= 1))
+                    fill.append(0 if gap <= 1 else int(gap))
+                prev = t
+        self.row = np.asarray(row, dtype=np.int64)
+        self.fwd = np.asarray(fwd, dtype=bool)
+        self.first = np.asarray(first, dtype=bool)
+        self.sep_n = np.asarray(sep_n, dtype=bool)
+        self.fill = np.asarray(fill, dtype=np.int64)
+        self.cand = np.flatnonzero(np.asarray(cand, dtype=bool))       # flat index of the RIGHT contig of every candidate
+        self.off = np.asarray(offsets, dtype=np.int64)[self.row] if len(row) else np.zeros(0, np.int64)
+        self.len = np.asarray(lengths, dtype=np.int64)[self.row] if len(row) else np.zeros(0, np.int64)
+
+    def candidates(self):
+        """-> (left row, right row, forward bits) of the junctions whose overlap has to be computed."""
+        c = self.cand
+        forward = self.fwd[c - 1].astype(np.uint8) | (self.fwd[c].astype(np.uint8) << 1)
+        return self.row[c - 1].astype(np.int32), self.row[c].astype(np.int32), forward
+
+    def pieces(self, overlaps):
+        """The piece table for the given raw overlaps (one per candidate).  Rows per contig: what precedes it (header,
+        'n' or the 'N' run) and its body; one '\\n' row per scaffold."""
+        nc, ns = len(self.row), len(self.scaffolds)
+        drop = np.zeros(nc, dtype=np.int64)
+        ov = np.asarray(overlaps, dtype=np.int64)
+        merged = ov >= MIN_MERGE_OVERLAP
+        drop[self.cand[merged]] = ov[merged]
+        headers = [('>' + name + '\n').encode('ascii') for name in self.names]
+        h_len = np.fromiter((len(h) for h in headers), dtype=np.int64, count=ns)
+        h_off = np.zeros(ns, dtype=np.int64)
+        if ns > 1:
+            np.cumsum(h_len[:-1], out=h_off[1:])
+        lit_n = int(h_len.sum())
+        literals = np.frombuffer(b''.join(headers) + b'n\n', dtype=np.uint8)
+        scaf_of = np.cumsum(self.first) - 1                           # scaffold ordinal of every contig
+        pre = 2 * np.arange(nc, dtype=np.int64) + scaf_of
+        n_rows = 2 * nc + ns
+        src = np.zeros(n_rows, dtype=np.int64)
+        length = np.zeros(n_rows, dtype=np.int64)
+        mode = np.full(n_rows, PIECE_LITERAL, dtype=np.uint8)
+        sep_n = self.sep_n | (drop > 0)
+        # what precedes the contig
+        src[pre] = np.where(self.first, h_off[scaf_of], lit_n)
+        length[pre] = np.where(self.first, h_len[scaf_of], np.where(sep_n, 1, self.fill))
+        mode[pre] = np.where(self.first | sep_n, PIECE_LITERAL, PIECE_FILL_N)
+        # the contig, oriented, without the merged bases
+        src[pre + 1] = self.off + np.where(self.fwd, drop, 0)
+        length[pre + 1] = self.len - drop
+        mode[pre + 1] = np.where(self.fwd, PIECE_COPY, PIECE_REVCOMP)
+        # the line end of every scaffold: the one row no contig claimed
+        is_nl = np.ones(n_rows, dtype=bool)
+        is_nl[pre] = False
+        is_nl[pre + 1] = False
+        src[is_nl] = lit_n + 1
+        length[is_nl] = 1
+        out_off = np.zeros(n_rows + 1, dtype=np.int64)
+        np.cumsum(length, out=out_off[1:])
+        self.drop, self.body_rows = drop, pre + 1
+        return dict(src_off=src, len=length, mode=mode, out_off=out_off, literals=literals,
+                    total=int(out_off[-1]), merges=[(int(c), int(drop[c])) for c in np.flatnonzero(drop > 0)])
+
+    def locate(self, emit_key, overlap_key):
+        """The reference's first KeyError from the two kernels' error words -> (flat contig, pool offset of the byte)."""
+        found = []
+        if emit_key != NO_ERROR:
+            c = int(np.searchsorted(self.body_rows, emit_key >> 32))
+            found.append((c, (emit_key & 0xFFFFFFFF) + int(self.drop[c])))
+        if overlap_key != NO_ERROR:
+            found.append((int(self.cand[overlap_key >> 32]), overlap_key & 0xFFFFFFFF))
+        if not found:
+            return None
+        c, pos = min(found)
+        return c, int(self.off[c] + self.len[c] - 1 - pos)      # reversed: oriented position pos is that far from the end
+
+
+class _Emitter(object):
+    """A layout on the device: overlaps computed, piece table uploaded, ranges of the FASTA on request."""
+
+    def __init__(self, F, param, store, unique_id, device=0):
+        t0 = time.time()
+        if unique_id is None:
+            unique_id = int(time.time())
+        self.own_store = store is None
+        if store is None:
+            ordered = [t for scaf in reversed(F) for t in sorted(scaf, key=lambda t: t[2])]
+            store = SequenceStore(range(len(ordered)), [t[4] for t in ordered], device=device)
+            index = None
+        else:
+            index = store.index
+        self.store = store
+        self.torch, self.dev = _torch_device(store.device.index)
+        torch, dev = self.torch, self.dev
+        self.lib = _lib.load()
+        self.layout = lay = ScaffoldLayout(F, param, unique_id, store.offsets, store.lengths, index)
+        t1 = time.time()
+        # overlaps of the candidate junctions
+        left, right, forward = lay.candidates()
+        self._err = torch.full((4,), -1, dtype=torch.int64, device=dev)   # [0] overlap, [2..3] emit
+        n = len(left)
+        if n:
+            d_left, d_right = torch.from_numpy(left).to(dev), torch.from_numpy(right).to(dev)
+            d_fwd = torch.from_numpy(forward).to(dev)
+            d_ov = torch.empty(n, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(self.lib.besst_dev_seq_overlaps(
+                    _C.c_void_p(stream), _C.c_void_p(store.pool_ptr), store.pool_bytes, len(store),
+                    _C.c_void_p(store._off.data_ptr()), _C.c_void_p(store._len.data_ptr()), n,
+                    _C.c_void_p(d_left.data_ptr()), _C.c_void_p(d_right.data_ptr()), _C.c_void_p(d_fwd.data_ptr()),
+                    lay.max_overlap, _C.c_void_p(d_ov.data_ptr()), _C.c_void_p(self._err.data_ptr())),
+                    'besst_dev_seq_overlaps')
+            overlaps = d_ov.cpu().numpy()
+            if (overlaps < 0).any():
+                raise BesstDeviceError('besst_dev_seq_overlaps: a junction names a contig outside the sequence store')
+        else:
+            overlaps = np.zeros(0, dtype=np.int32)
+        self.overlaps = overlaps
+        t2 = time.time()
+        tab = self.table = lay.pieces(overlaps)
+        self.total = tab['total']
+        self._lit, self._lit_ptr = _padded_upload(torch, dev, tab['literals'])
+        self._src = torch.from_numpy(tab['src_off']).to(dev)
+        self._len = torch.from_numpy(tab['len']).to(dev)
+        self._mode = torch.from_numpy(tab['mode']).to(dev)
+        self._out_off = torch.from_numpy(tab['out_off']).to(dev)
+        torch.cuda.synchronize(dev)
+        t3 = time.time()
+        self.seconds = dict(layout=t1 - t0, overlaps=t2 - t1, table=t3 - t2)
+
+    def emit(self, begin, end, out, stream=None):
+        """Enqueue bytes [begin, end) of the FASTA into the uint8 device tensor ``out`` (16-byte aligned)."""
+        torch = self.torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.dev)
+        p = _C.c_void_p
+        _lib.check(self.lib.besst_dev_emit_scaffolds(
+            p(stream.cuda_stream), p(self.store.pool_ptr), self.store.pool_bytes, p(self._lit_ptr),
+            int(self.table['literals'].shape[0]), len(self.table['mode']), p(self._src.data_ptr()),
+            p(self._len.data_ptr()), p(self._mode.data_ptr()), p(self._out_off.data_ptr()), int(begin), int(end),
+            p(out.data_ptr()), p(self._err.data_ptr() + 16)), 'besst_dev_emit_scaffolds')
+
+    def key_error(self):
+        """After the last range: None, or (flat contig index, KeyError to raise) like the reference's first failure."""
+        self.torch.cuda.synchronize(self.dev)
+        err = self._err.cpu().numpy().view(np.uint64)
+        if int(err[3]) != NO_ERROR:
+            raise BesstDeviceError('besst_dev_emit_scaffolds: piece %d points outside its pool' % int(err[3]))
+        hit = self.layout.locate(int(err[2]), int(err[0]))
+        if hit is None:
+            return None
+        return hit[0], KeyError(chr(self.store.byte_at(hit[1])))
+
+    def merging_lines(self, before=None):
+        return ['merging {0} bp here'.format(n) for c, n in self.table['merges'] if before is None or c < before]
+
+    def close(self):
+        if self.own_store:
+            self.store.close()
+        self._lit = self._src = self._len = self._mode = self._out_off = self._err = None
+
+
+def _report(em, param):
+    """The `merging` lines the reference prints up to its first KeyError, then that error."""
+    bad = em.key_error()
+    for line in em.merging_lines(None if bad is None else bad[0]):
+        print(line, file=param.information_file)
+    if bad is not None:
+        raise bad[1]
+
+
+def scaffold_bytes(F, param, store=None, unique_id=None, chunk_bytes=None):
+    """The FASTA text PrintOutput would write, as bytes (``chunk_bytes``: produced in ranges of that many bytes)."""
+    em = _Emitter(F, param, store, unique_id)
+    try:
+        torch, total = em.torch, em.total
+        step = total if not chunk_bytes else int(chunk_bytes)
+        parts = []
+        with torch.cuda.device(em.dev):
+            buf = torch.empty(max(16, (min(step, total) + 15) // 16 * 16), dtype=torch.uint8, device=em.dev)
+            for begin in range(0, total, max(step, 1)):
+                end = min(total, begin + step)
+                em.emit(begin, end, buf)
+                parts.append(buf[:end - begin].cpu().numpy().tobytes())
+        _report(em, param)
+        return b''.join(parts)
+    finally:
+        em.close()
+
+
+def _write_fasta_chunks(em, path, chunk_bytes):
+    """emit_kernel -> device buffer -> pinned buffer -> file, two of each: the copy and the write of chunk c run while the
+    kernel of chunk c + 1 does.  -> seconds spent in (kernels, copies, file writes)."""
+    torch, dev, total = em.torch, em.dev, em.total
+    size = max(16, (min(chunk_bytes, total) + 15) // 16 * 16)
+    t_kernel = t_copy = t_write = 0.0
+    with torch.cuda.device(dev), open(path, 'wb') as fh:
+        d_buf = [torch.empty(size, dtype=torch.uint8, device=dev) for _ in range(2)]
+        h_buf = [torch.empty(size, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        compute, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+        pending = []                                             # (slot, bytes, events) of chunks not yet written
+
+        def drain():
+            nonlocal t_kernel, t_copy, t_write
+            slot, n, (k0, k1, c0, c1) = pending.pop(0)
+            c1.synchronize()
+            t_kernel += k0.elapsed_time(k1) * 1e-3
+            t_copy += c0.elapsed_time(c1) * 1e-3
+            t0 = time.time()
+            fh.write(memoryview(h_buf[slot].numpy())[:n])
+            t_write += time.time() - t0
+
+        for i, begin in enumerate(range(0, total, size)):
+            end, slot = min(total, begin + size), i % 2
+            if len(pending) == 2:
+                drain()                                          # frees this slot's two buffers
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record(compute)
+            em.emit(begin, end, d_buf[slot], compute)
+            ev[1].record(compute)
+            copy.wait_event(ev[1])
+            with torch.cuda.stream(copy):
+                ev[2].record(copy)
+                h_buf[slot][:end - begin].copy_(d_buf[slot][:end - begin], non_blocking=True)
+                ev[3].record(copy)
+            pending.append((slot, end - begin, ev))
+        while pending:
+            drain()
+    return t_kernel, t_copy, t_write
+
+
+def _write_agp_gff(layout, agp, gff):
+    """reference :153-195: coordinates from positions and lengths as given; merges and the one-letter 'n' do not show."""
+    print('##gff-version 3', file=gff)
+    print('##agp-version 2.0\n#lw-scaffolder output', file=agp)
+    for name, scaf in zip(layout.names, layout.scaffolds):
+        component = 0
+        prev_end = None
+        for i, (contig, direction, position, length, _seq) in enumerate(scaf):
+            sign = '+' if direction else '-'
+            first, last = position, position + length - 1
+            if i > 0 and first - (prev_end + 1) > 0:
+                gap = first - (prev_end + 1)
+                component += 1
+                print('\t'.join(str(x) for x in (name, prev_end + 2, first, component, 'N', gap, 'scaffold', 'yes',
+                                                 'paired-ends')), file=agp)
+                print('\t'.join(str(x) for x in (name, 'besst_assembly', 'gap', prev_end + 2, first, '.', '.', '.', '')),
+                      file=gff)
+            component += 1
+            print('\t'.join(str(x) for x in (name, first + 1, last + 1, component, 'W', contig, '1', last - first + 1,
+                                             sign)), file=agp)
+            short = '_'.join(contig.split('_', 2)[:2])
+            print('\t'.join(str(x) for x in (name, 'besst_assembly', 'contig', first + 1, last + 1, '.', sign, '.',
+                                             'ID=' + contig + ';Name=' + short)), file=gff)
+            prev_end = last
+
+
+def PrintOutput(F, Information, output_dest, param, pass_nr, store=None, unique_id=None):
+    pass_dir = param.output_directory + '/pass' + str(pass_nr)
+    try:
+        os.mkdir(pass_dir)
+    except OSError:
+        pass
+    print('(super)Contigs after scaffolding: ' + str(len(F)) + '\n', file=Information)
+    t_start = time.time()
+    fasta = pass_dir + '/Scaffolds-pass' + str(pass_nr) + '.fa'
+    em = _Emitter(F, param, store, unique_id)
+    try:
+        partial = fasta + '.partial'
+        try:
+            t_kernel, t_copy, t_write = _write_fasta_chunks(em, partial, CHUNK_BYTES)
+            _report(em, param)
+        except BaseException:
+            if os.path.exists(partial):
+                os.remove(partial)
+            raise
+        os.replace(partial, fasta)
+        t0 = time.time()
+        with open(pass_dir + '/info-pass' + str(pass_nr) + '.gff', 'w') as gff, \
+                open(pass_dir + '/info-pass' + str(pass_nr) + '.agp', 'w') as agp:
+            _write_agp_gff(em.layout, agp, gff)
+        last_timings.clear()
+        last_timings.update(em.seconds, emit_kernels=t_kernel, d2h=t_copy, file_write=t_write,
+                            agp_gff=time.time() - t0, total=time.time() - t_start, fasta_bytes=em.total)
+    finally:
+        em.close()
     return ()

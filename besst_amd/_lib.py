@@ -208,6 +208,14 @@ _SIGNATURES = {
     'besst_dev_linearize_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
     'besst_dev_linearize': (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P,
                                       _P]),
+    'besst_host_complement_table': (_P, []),
+    'besst_dev_seq_overlaps': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P]),
+    'besst_host_seq_overlaps': (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P,
+                                          _P]),
+    'besst_dev_emit_scaffolds': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_int64,
+                                           C.c_int64, _P, _P]),
+    'besst_host_emit_scaffolds': (C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_int64,
+                                            C.c_int64, _P, _P]),
 }
 
 _lib = None

@@ -4,8 +4,10 @@
 
 Flag names and defaults follow runBESST:254-402 for everything the hot path reads (-m -s -T -k -r -e -z -z_min
 --min_mapq -d -y --no_score).  Per library it runs the BAM front-end, ``libmetrics.get_metrics`` and
-``CreateGraph.PE`` and writes Statistics.txt plus the scored edge tables of G and G' as TSV; scaffolding itself
-(MakeScaffolds and later) stays with BESST - see INTEGRATION.md for plugging these calls into runBESST.
+``CreateGraph.PE`` and writes Statistics.txt plus the scored edge tables of G and G' as TSV.  With ``--scaffolds -y`` it
+goes on like runBESST's loop without path extension: the graph is linearised, the paths become scaffolds, and every pass
+writes ``pass<n>/Scaffolds-pass<n>.fa`` with its ``.agp`` and ``.gff`` (the sequence work on the GPU).  BESST's path
+search (PROWithinScaf / PROBetweenScaf) stays with BESST - see INTEGRATION.md for plugging these calls into runBESST.
 
 Several GPUs of one node: launch the same command line under torchrun, one process per GPU -
 
@@ -22,8 +24,9 @@ import sys
 from time import time
 
 from . import CreateGraph as CG
+from . import GenerateOutput as GO
 from . import MakeScaffolds as MS
-from . import Parameter, bamio, libmetrics, session
+from . import Parameter, bamio, libmetrics, mathstats_compat, session
 
 
 def read_fasta(path):
@@ -60,6 +63,12 @@ def build_parser():
     ap.add_argument('-d', dest='duplicate', action='store_false', help='switch duplicate detection off')
     ap.add_argument('-y', dest='extendpaths', action='store_false', help='switch path extension off')
     ap.add_argument('--no_score', dest='no_score', action='store_true')
+    ap.add_argument('-max_contig_overlap', dest='max_contig_overlap', type=int, default=200,
+                    help='longest overlap between neighbouring contig ends that is looked for when scaffolds are written')
+    ap.add_argument('--scaffolds', action='store_true',
+                    help='per pass: linearise the graph, chain the paths into scaffolds (MakeScaffolds.Algorithm without '
+                         'path extension) and write Scaffolds-pass<n>.fa, info-pass<n>.agp and info-pass<n>.gff; needs -y '
+                         'and scoring')
     ap.add_argument('--threads', type=int, default=None, help='BAM inflate threads')
     ap.add_argument('--linearize', action='store_true',
                     help="also run steps 1-4 of MakeScaffolds.Algorithm on a copy of G (isolated scaffolds, "
@@ -80,6 +89,30 @@ def write_edges(path, G):
                 continue
             print('\t'.join(str(x) for x in (u[0], u[1], v[0], v[1], d['nr_links'], d['obs'], d['obs_sq'],
                                              d.get('gap', ''), d.get('score', ''))), file=fh)
+
+
+def write_scaffolds(G, G_prime, Contigs, small_contigs, Scaffolds, small_scaffolds, Information, param, pass_nr, store):
+    """MakeScaffolds.Algorithm with extend_paths off (MakeScaffolds.py:66-90) on the pass's own graphs and dicts - the
+    next library sees the new contig table - then runBESST:205-218: every scaffold to F, F to the three output files."""
+    t0 = time()
+    dValuesTable = None
+    if param.std_dev_ins_size:
+        dValuesTable = mathstats_compat.PreCalcMLvaluesOfdLongContigs(param.mean_ins_size, param.std_dev_ins_size,
+                                                                      param.read_len)
+    G, Contigs, Scaffolds = MS.LinearizeGraph(G, G_prime, Contigs, Scaffolds, Information, param)
+    MS.NewContigsScaffolds(G, G_prime, Contigs, small_contigs, Scaffolds, small_scaffolds, Information, dValuesTable, param,
+                           set())
+    print('Time elapsed for making scaffolds, iteration ' + str(pass_nr - 1) + ': ' + str(time() - t0) + '\n',
+          file=Information)
+    t0 = time()
+    F = []
+    for scaffold_ in small_scaffolds:
+        F = GO.WriteToF(F, small_contigs, small_scaffolds[scaffold_].contigs)
+    for scaffold_ in Scaffolds:
+        F = GO.WriteToF(F, Contigs, Scaffolds[scaffold_].contigs)
+    GO.PrintOutput(F, Information, param.output_directory, param, pass_nr, store=store)
+    print('Time elapsed for writing the scaffolds, iteration ' + str(pass_nr - 1) + ': ' + str(time() - t0) + '\n',
+          file=Information)
 
 
 def join_process_group():
@@ -108,6 +141,14 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if len(args.orientation) != len(args.bamfiles):
         sys.exit('need one -orientation per BAM file')
+    if args.scaffolds and args.extendpaths:
+        sys.exit('--scaffolds needs -y: with path extension on, BESST places contigs with its path search '
+                 '(PROWithinScaf / PROBetweenScaf), which is not part of this package - the scaffolds would not be BESST\'s')
+    if args.scaffolds and args.no_score:
+        sys.exit('--scaffolds cannot be combined with --no_score: without scores BESST skips the linearisation and the '
+                 'scaffold step, and its path search, which would do the work instead, is not part of this package')
+    if args.max_contig_overlap < 0 or args.max_contig_overlap > GO.MAX_CONTIG_OVERLAP_LIMIT:
+        sys.exit('-max_contig_overlap must lie in 0..%d' % GO.MAX_CONTIG_OVERLAP_LIMIT)
     rank, joined = join_process_group()
     try:
         return _run(args, rank)
@@ -131,7 +172,7 @@ def _run(args, rank):
     param.extend_paths = args.extendpaths
     param.detect_haplotype = False
     param.print_scores = False
-    param.max_contig_overlap = 200
+    param.max_contig_overlap = args.max_contig_overlap
     param.output_directory = out
     param.first_lib = True
     Information = param.information_file = open(os.path.join(out, 'Statistics.txt') if lead else os.devnull, 'w')
@@ -139,6 +180,8 @@ def _run(args, rank):
     if lead:
         print('Number of initial contigs:', len(C_dict))
     Contigs, Scaffolds, small_contigs, small_scaffolds = {}, {}, {}, {}
+    # the sequences go to the GPU once, before CreateGraph.PE drops repeats and low-coverage contigs from its dicts
+    store = GO.SequenceStore(list(C_dict), list(C_dict.values())) if args.scaffolds and lead else None
     for i, bam in enumerate(args.bamfiles):
         param.pass_number = i + 1
         param.bamfile = bam
@@ -181,9 +224,13 @@ def _run(args, rank):
             print('Time elapsed for the graph linearisation (steps 1-4), iteration ' + str(i) + ': ' + str(time() - t0)
                   + '\n', file=Information)
             write_edges(os.path.join(pass_dir, 'edges_G_linear.tsv'), L)
+        if args.scaffolds:
+            write_scaffolds(G, G_prime, Contigs, small_contigs, Scaffolds, small_scaffolds, Information, param, i + 1, store)
         print('pass %d: %d records, G %d link edges, G_prime %d link edges' % (
             i + 1, len(records), sum(1 for u, v in G.edges() if G[u][v]['nr_links'] is not None),
             sum(1 for u, v in G_prime.edges() if G_prime[u][v]['nr_links'] is not None)))
+    if store is not None:
+        store.close()
     Information.close()
     return 0
 

@@ -36,7 +36,8 @@ extern "C" {
 
 /* 1: rounds 1-4.  2: + the sharded-scan and BAM-slice entry points of round 5 and the log-normal scoring entry points of
  * round 6 (additions only: a caller built against 1 keeps working).  3: besst_lib_params grew by `mate_bits` (a caller
- * built against 2 passes a shorter struct: recompile), + besst_dev_mate_bits. */
+ * built against 2 passes a shorter struct: recompile), + besst_dev_mate_bits.  Added since without a new version
+ * (additions only): the scaffold-output entry points besst_{dev,host}_seq_overlaps / besst_{dev,host}_emit_scaffolds. */
 #define BESST_ABI_VERSION 3
 
 /* status codes */
@@ -703,6 +704,56 @@ int besst_score_paths(int device, int64_t n_nodes, const int64_t* row_ptr, const
 int besst_dev_score_paths(void* stream, int64_t n_nodes, const int64_t* row_ptr, const int32_t* col,
                           const int32_t* weight, int64_t n_paths, const int64_t* path_ptr,
                           const int32_t* path_nodes, int32_t contamination, int64_t* good, int64_t* bad);
+
+/* ---- scaffold output: the sequence work of GenerateOutput.PrintOutput (GenerateOutput.py:88-234) ---------------------
+ * The contigs of a run lie end to end in one byte pool (one byte per base, as read: case and IUPAC codes survive);
+ * contig i is pool[ctg_off[i] .. ctg_off[i] + ctg_len[i]).  Device pools (besst_dev_*) must have BESST_EMIT_PAD readable
+ * bytes before `pool` and after pool + pool_bytes, and so must `literals`: the kernels read whole aligned dwords around
+ * the bytes they need.  The host-pointer twins add the pads themselves.
+ *
+ * besst_*_seq_overlaps: check_kmer_overlap (:110-116) for n junctions.  Junction c joins contig left[c] to contig
+ * right[c]; forward[c] bit 0 / bit 1: the left / right contig is written as stored (else reverse-complemented).
+ *   overlap[c]   the largest i >= 1 for which the last i bytes of the last max_overlap bytes of the oriented left contig
+ *                equal the first i bytes of the first max_overlap bytes of the oriented right one, else 0 (bytes
+ *                compare as bytes; a window shorter than max_overlap is the whole contig); -1 for a junction whose
+ *                contig indices or pool range are invalid (device layer; the host layer refuses those up front)
+ *   err[0]       min over the junctions whose reversed RIGHT window holds a byte without a complement of
+ *                (c << 32 | position of that byte in the oriented window); the caller sets it to all ones
+ * max_overlap: 0..BESST_MAX_CONTIG_OVERLAP.
+ *
+ * besst_*_emit_scaffolds: bytes [begin, end) of the output, written to out[0 .. end - begin).  Piece p supplies the output
+ * bytes [out_off[p], out_off[p + 1]) (out_off: n_pieces + 1 entries, the exclusive prefix sum of len, out_off[0] = 0):
+ *   BESST_PIECE_COPY     pool[src_off .. src_off + len)
+ *   BESST_PIECE_REVCOMP  the same bytes reverse-complemented (the table of GenerateOutput.rev_nuc)
+ *   BESST_PIECE_FILL_N   len times 'N' (src_off unused)
+ *   BESST_PIECE_LITERAL  literals[src_off .. src_off + len): headers, '\n', 'n'
+ *   err[0]       min over the REVCOMP bytes without a complement of (p << 32 | position in the piece's output); the
+ *                reference raises KeyError there.  The call completes; such bytes come out as 0.
+ *   err[1]       min p of the rows that point outside their pool (device layer; their bytes come out as '?')
+ * The caller sets both words to all ones before the first range.  `out` of the device form is 16-byte aligned.
+ * besst_host_complement_table: the 256-entry complement table, 0 = no complement. */
+#define BESST_MAX_CONTIG_OVERLAP 4096
+#define BESST_EMIT_PAD 32
+#define BESST_PIECE_COPY 0
+#define BESST_PIECE_REVCOMP 1
+#define BESST_PIECE_FILL_N 2
+#define BESST_PIECE_LITERAL 3
+const uint8_t* besst_host_complement_table(void);
+int besst_dev_seq_overlaps(void* stream, const uint8_t* pool, int64_t pool_bytes, int64_t n_contigs,
+                           const int64_t* ctg_off, const int32_t* ctg_len, int64_t n, const int32_t* left,
+                           const int32_t* right, const uint8_t* forward, int32_t max_overlap, int32_t* overlap,
+                           uint64_t* err);
+int besst_host_seq_overlaps(int device, const uint8_t* pool, int64_t pool_bytes, int64_t n_contigs, const int64_t* ctg_off,
+                            const int32_t* ctg_len, int64_t n, const int32_t* left, const int32_t* right,
+                            const uint8_t* forward, int32_t max_overlap, int32_t* overlap, uint64_t* err);
+int besst_dev_emit_scaffolds(void* stream, const uint8_t* pool, int64_t pool_bytes, const uint8_t* literals,
+                             int64_t literal_bytes, int64_t n_pieces, const int64_t* src_off, const int64_t* len,
+                             const uint8_t* mode, const int64_t* out_off, int64_t begin, int64_t end, uint8_t* out,
+                             uint64_t* err);
+int besst_host_emit_scaffolds(int device, const uint8_t* pool, int64_t pool_bytes, const uint8_t* literals,
+                              int64_t literal_bytes, int64_t n_pieces, const int64_t* src_off, const int64_t* len,
+                              const uint8_t* mode, const int64_t* out_off, int64_t begin, int64_t end, uint8_t* out,
+                              uint64_t* err);
 
 #ifdef __cplusplus
 }
