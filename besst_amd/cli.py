@@ -95,6 +95,9 @@ def write_scaffolds(G, G_prime, Contigs, small_contigs, Scaffolds, small_scaffol
     """MakeScaffolds.Algorithm with extend_paths off (MakeScaffolds.py:66-90) on the pass's own graphs and dicts - the
     next library sees the new contig table - then runBESST:205-218: every scaffold to F, F to the three output files."""
     t0 = time()
+    # the two lines Algorithm opens with (MakeScaffolds.py:51-57)
+    print(str(sum(1 for u, v in G.edges() if G[u][v]['nr_links'])) + ' link edges created.', file=Information)
+    print('Perform inference on scaffold graph...', file=Information)
     dValuesTable = None
     if param.std_dev_ins_size:
         dValuesTable = mathstats_compat.PreCalcMLvaluesOfdLongContigs(param.mean_ins_size, param.std_dev_ins_size,

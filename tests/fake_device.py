@@ -201,3 +201,64 @@ def fake_chain_arrays(n_scaffolds, link, gap, scaffold_length, node_order, devic
             steps += 1
         terminal[h], beyond[h], lowest[h] = cur, dist, low
     return terminal, beyond, lowest, 0
+
+
+def fake_linearize_arrays(n_scaffolds, a, b, score, steps=15, device=0):
+    """Sequential stand-in for besst_amd.MakeScaffolds.linearize_arrays (besst_linearize, csrc/linearize.hip) with all
+    four steps asked for, put together from the steps of oracle/scaffold_oracle.py: the same dict, `removed_by` 1, 3 or 4
+    by the step that removed the scaffold."""
+    from oracle import scaffold_oracle as SO
+    assert steps == 15, 'the stand-in answers LinearizeGraph only'
+    n, a, b, score = int(n_scaffolds), [int(x) for x in a], [int(x) for x in b], [float(x) for x in score]
+    removed_by = np.zeros(n, np.uint8)
+
+    def degrees(alive):
+        deg = [0] * (2 * n)
+        for i in range(len(a)):
+            if alive[i]:
+                deg[a[i]] += 1
+                deg[b[i]] += 1
+        return deg
+
+    def mark(present, step):
+        for k in range(n):
+            if not present[k] and removed_by[k] == 0:
+                removed_by[k] = step
+    present = [True] * n
+    iso1 = SO.remove_isolated(n, present, degrees([True] * len(a)))
+    mark(present, 1)
+    alive, events = SO.remove_ambiguous(2 * n, a, b, score)
+    iso3 = SO.remove_isolated(n, present, degrees(alive))
+    mark(present, 3)
+    cycles, on_cycle = SO.cycle_scaffolds(n, present, a, b, alive)
+    for k in on_cycle:
+        present[k] = False
+    mark(present, 4)
+    return dict(alive2=np.array(alive, bool), removed_by=removed_by, present=removed_by == 0, isolated=[iso1, iso3],
+                cycles=cycles, rounds=0, ambivalent=events)
+
+
+def fake_print_output(F, Information, output_dest, param, pass_nr, store=None, unique_id=None):
+    """Stand-in for besst_amd.GenerateOutput.PrintOutput without the device: the package's own layout, piece table and
+    AGP / GFF writer, with the two kernels answered by the models of tests/output_util.py (window_overlap for
+    seq_overlap_kernel, apply_pieces for emit_kernel).  Sequences come from the tuples of F."""
+    import os
+    from besst_amd import GenerateOutput as GO
+    from tests import output_util as OU
+    pass_dir = os.path.join(param.output_directory, 'pass' + str(pass_nr))
+    os.makedirs(pass_dir, exist_ok=True)
+    print('(super)Contigs after scaffolding: ' + str(len(F)) + '\n', file=Information)
+    if unique_id is None:
+        unique_id = int(GO.time.time())
+    flat = [t for scaf in OU.ordered(F) for t in scaf]
+    pool, off, length = GO.pack_sequences([t[4] for t in flat])
+    lay = GO.ScaffoldLayout(F, param, unique_id, off, length)
+    tab = lay.pieces([OU.window_overlap(flat[c - 1], flat[c], lay.max_overlap) for c in lay.cand.tolist()])
+    with open(os.path.join(pass_dir, 'Scaffolds-pass%d.fa' % pass_nr), 'wb') as fh:
+        fh.write(OU.apply_pieces(tab, pool))
+    for _, n in tab['merges']:
+        print('merging {0} bp here'.format(n), file=param.information_file)
+    with open(os.path.join(pass_dir, 'info-pass%d.gff' % pass_nr), 'w') as gff, \
+            open(os.path.join(pass_dir, 'info-pass%d.agp' % pass_nr), 'w') as agp:
+        GO._write_agp_gff(lay, agp, gff)
+    return ()
