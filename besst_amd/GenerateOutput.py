@@ -8,7 +8,9 @@ they DELETE the removed contigs from the caller's dicts.
 :class:`SequenceStore` in HBM for the whole run, ``seq_overlap_kernel`` finds the overlaps of the junctions that may
 merge, the host turns placements + overlaps into a piece table with numpy, and ``emit_kernel`` gathers the FASTA bytes
 (copy / reverse-complement / 'N' fill) in chunks that are copied back and written while the next chunk is produced.
-AGP and GFF are plain text from names, positions and gaps.  Like the rest of the package there is no CPU path: without
+AGP and GFF are plain text from names, positions and gaps.  ``SequenceStore.from_fasta`` fills the store from the contig
+FASTA itself (csrc/fasta.hip: the file's bytes are parsed in HBM by the rules of runBESST:45-74); ``C_dict`` then holds
+:class:`SequenceRef` handles instead of strings.  Like the rest of the package there is no CPU path: without
 the library or a GPU these calls raise :class:`besst_amd._lib.BesstDeviceError`.
 """
 from __future__ import print_function
@@ -174,6 +176,47 @@ class SequenceStore(object):
         objs = list(Contigs.values()) + list(small_contigs.values())
         return cls([c.name for c in objs], [c.sequence for c in objs], device=device)
 
+    @classmethod
+    def from_fasta(cls, path, device=0, tile_bytes=None):
+        """The store of a contig FASTA, parsed on the device (csrc/fasta.hip) with the rules of the reference's
+        ReadInContigseqs (runBESST:45-74): one row per header line in file order (``names``); ``index[name]`` is the row
+        of the name's last occurrence.  ValueError: a byte outside ASCII, a header without a name, a contig of 2^31 bases
+        or more."""
+        torch, dev = _torch_device(device)
+        with torch.cuda.device(dev):
+            text, n = _upload_file(torch, dev, path)
+            parsed = parse_fasta_text(text, n, tile_bytes)
+            del text
+        self = cls.__new__(cls)
+        self.device = dev
+        self._pool, self.pool_ptr, self.pool_bytes = parsed['pool'], parsed['pool'].data_ptr() + EMIT_PAD, parsed['pool_bytes']
+        self._off, self._len = parsed['ctg_off'], parsed['ctg_len']
+        self.offsets, self.lengths = self._off.cpu().numpy(), self._len.cpu().numpy()
+        blob, at = parsed['names'].cpu().numpy().tobytes().decode('ascii'), parsed['name_off'].cpu().numpy().tolist()
+        self.names = [blob[a:b] for a, b in zip(at[:-1], at[1:])]
+        self.index = {name: i for i, name in enumerate(self.names)}
+        return self
+
+    def fetch(self, row):
+        """The bytes of contig ``row``, copied back from the pool."""
+        off, length = int(self.offsets[row]), int(self.lengths[row])
+        return self._pool[EMIT_PAD + off:EMIT_PAD + off + length].cpu().numpy().tobytes()
+
+    def contig_dict(self, filter_length=None, Information=None):
+        """name -> SequenceRef in the reference's dictionary order (a name that occurs twice: the place of its first
+        occurrence, the sequence of its last), the way CreateGraph.PE takes ``C_dict``.  ``filter_length``: -filter_contigs
+        (runBESST:67-73) - shorter contigs are left out; their bases stay in the pool, unused.  With ``Information`` the
+        reference's two lines are printed to it."""
+        names = getattr(self, 'names', None)
+        if names is None:
+            names = sorted(self.index, key=self.index.get)
+        contigs = {}
+        for name in names:
+            if name not in contigs:
+                row = self.index[name]
+                contigs[name] = SequenceRef(self, row, int(self.lengths[row]))
+        return filter_contigs(contigs, filter_length, Information)
+
     def __len__(self):
         return len(self.offsets)
 
@@ -189,6 +232,135 @@ class SequenceStore(object):
 
     def __exit__(self, *exc):
         self.close()
+
+
+class SequenceRef(object):
+    """A contig's sequence that stays in the store: what InitializeObjects and the repeat / low-coverage FASTA writers ask
+    of a sequence (len, truth, slices, str) without the bases in host memory.  The first use that needs bases fetches them
+    once."""
+    __slots__ = ('store', 'row', 'length', '_bytes')
+
+    def __init__(self, store, row, length):
+        self.store, self.row, self.length, self._bytes = store, row, length, None
+
+    def __len__(self):
+        return self.length
+
+    def __bool__(self):
+        return self.length > 0
+
+    def _fetched(self):
+        if self._bytes is None:
+            self._bytes = self.store.fetch(self.row)
+        return self._bytes
+
+    def __getitem__(self, key):
+        got = self._fetched()[key]
+        return chr(got) if isinstance(got, int) else got.decode('ascii')
+
+    def __str__(self):
+        return self._fetched().decode('ascii')
+
+
+def filter_contigs(contigs, filter_length, Information=None):
+    """-filter_contigs as runBESST:65-73 meant it (on Python 3 the reference raises RuntimeError here: it deletes from the
+    dict whose keys it walks): contigs shorter than ``filter_length`` leave the dict.  The two lines go to ``Information``
+    in the reference's words."""
+    if Information is not None:
+        print('Initial number of contigs: {}. '.format(len(contigs)), file=Information)
+    if filter_length:
+        short = [name for name, seq in contigs.items() if len(seq) < filter_length]
+        for name in short:
+            del contigs[name]
+        if Information is not None:
+            print('Number of contigs discarded from further analysis (with -filter_contigs set to {0}): {1}'.format(
+                filter_length, len(short)), file=Information)
+    return contigs
+
+
+class FastaError(ValueError):
+    """The contig FASTA cannot be read; ``offset``: the byte of the file at fault."""
+
+    def __init__(self, message, offset):
+        ValueError.__init__(self, message)
+        self.offset = offset
+
+
+UPLOAD_CHUNK = 32 << 20                  # from_fasta reads the file through two pinned buffers of this size
+FASTA_INFO_WORDS = 6                     # include/besst_amd.h: BESST_FASTA_INFO_WORDS
+
+
+def _upload_file(torch, dev, path):
+    """file -> pinned buffer -> HBM, two buffers and a side stream: the read of chunk c + 1 runs while chunk c is copied.
+    -> (uint8 tensor of the file's bytes followed by EMIT_PAD zero bytes, number of bytes)"""
+    with open(path, 'rb', buffering=0) as fh:
+        n = os.fstat(fh.fileno()).st_size
+        text = torch.empty(n + EMIT_PAD, dtype=torch.uint8, device=dev)
+        text[n:].zero_()
+        size = max(1, min(UPLOAD_CHUNK, n))
+        h_buf = [torch.empty(size, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        views = [memoryview(b.numpy()) for b in h_buf]
+        done = [None, None]
+        copy = torch.cuda.Stream(dev)
+        copy.wait_stream(torch.cuda.current_stream(dev))
+        at, i = 0, 0
+        while at < n:
+            slot = i % 2
+            if done[slot] is not None:
+                done[slot].synchronize()                        # the buffer's last copy has left it
+            got = fh.readinto(views[slot][:min(size, n - at)])
+            if not got:
+                raise IOError('%s ended %d bytes early' % (path, n - at))
+            with torch.cuda.stream(copy):
+                text[at:at + got].copy_(h_buf[slot][:got], non_blocking=True)
+                done[slot] = torch.cuda.Event()
+                done[slot].record(copy)
+            at += got
+            i += 1
+        torch.cuda.current_stream(dev).wait_stream(copy)
+        copy.synchronize()                                       # the pinned buffers are let go here
+    return text, n
+
+
+def parse_fasta_text(text, n, tile_bytes=None):
+    """The FASTA bytes ``text[:n]`` (uint8 device tensor with EMIT_PAD readable bytes behind them) -> dict(pool: padded
+    uint8 tensor, pool_bytes, ctg_off, ctg_len, names, name_off: device tensors).  Raises ValueError the way
+    SequenceStore.from_fasta documents."""
+    import torch
+    lib = _lib.load()
+    dev = text.device
+    tile = int(tile_bytes or 0)
+    p = _C.c_void_p
+    ws_bytes = lib.besst_dev_fasta_workspace_bytes(int(n), tile)
+    if not ws_bytes:
+        raise ValueError('tile_bytes must be a multiple of 1024 in 1024..65536')
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        info = torch.empty(FASTA_INFO_WORDS, dtype=torch.int64, device=dev)
+        _lib.check(lib.besst_dev_fasta_scan(p(stream), p(text.data_ptr()), int(n), tile, p(ws.data_ptr()), ws_bytes,
+                                            p(info.data_ptr())), 'besst_dev_fasta_scan')
+        n_contigs, pool_bytes, names_bytes, first_error = info.cpu().numpy().view(np.uint64)[:4].tolist()
+        if first_error != NO_ERROR:
+            if int(text[first_error].item()) >= 128:
+                raise FastaError('contig sequences must be ASCII: byte %d of the FASTA file is not' % first_error,
+                                 first_error)
+            raise FastaError('the header line at byte %d of the FASTA file has no name' % first_error, first_error)
+        pool = torch.empty(pool_bytes + 2 * EMIT_PAD, dtype=torch.uint8, device=dev)
+        pool[:EMIT_PAD].zero_()
+        pool[EMIT_PAD + pool_bytes:].zero_()
+        ctg_off = torch.empty(n_contigs, dtype=torch.int64, device=dev)
+        ctg_len = torch.empty(n_contigs, dtype=torch.int32, device=dev)
+        names = torch.empty(max(1, names_bytes), dtype=torch.uint8, device=dev)
+        name_off = torch.empty(n_contigs + 1, dtype=torch.int64, device=dev)
+        _lib.check(lib.besst_dev_fasta_pack(p(stream), p(text.data_ptr()), int(n), tile, p(ws.data_ptr()), ws_bytes,
+                                            p(info.data_ptr()), n_contigs, pool_bytes, names_bytes,
+                                            p(pool.data_ptr() + EMIT_PAD), p(ctg_off.data_ptr()), p(ctg_len.data_ptr()),
+                                            p(names.data_ptr()), p(name_off.data_ptr())), 'besst_dev_fasta_pack')
+        if info.cpu().numpy().view(np.uint64)[4] != NO_ERROR:
+            raise ValueError('a contig of 2^31 bases or more')
+    return dict(pool=pool, pool_bytes=int(pool_bytes), ctg_off=ctg_off, ctg_len=ctg_len, names=names[:names_bytes],
+                name_off=name_off)
 
 
 class ScaffoldLayout(object):

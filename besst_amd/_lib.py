@@ -216,6 +216,10 @@ _SIGNATURES = {
                                            C.c_int64, _P, _P]),
     'besst_host_emit_scaffolds': (C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_int64,
                                             C.c_int64, _P, _P]),
+    'besst_dev_fasta_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
+    'besst_dev_fasta_scan': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
+    'besst_dev_fasta_pack': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P, C.c_int64, C.c_int64, C.c_int64,
+                                       _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -3,10 +3,11 @@
     python -m besst_amd.cli -c contigs.fa -f lib1.bam [lib2.bam ...] -orientation fr [rf ...] -o outdir
 
 Flag names and defaults follow runBESST:254-402 for everything the hot path reads (-m -s -T -k -r -e -z -z_min
---min_mapq -d -y --no_score).  Per library it runs the BAM front-end, ``libmetrics.get_metrics`` and
+--min_mapq -d -y --no_score -filter_contigs).  Per library it runs the BAM front-end, ``libmetrics.get_metrics`` and
 ``CreateGraph.PE`` and writes Statistics.txt plus the scored edge tables of G and G' as TSV.  With ``--scaffolds -y`` it
 goes on like runBESST's loop without path extension: the graph is linearised, the paths become scaffolds, and every pass
-writes ``pass<n>/Scaffolds-pass<n>.fa`` with its ``.agp`` and ``.gff`` (the sequence work on the GPU).  BESST's path
+writes ``pass<n>/Scaffolds-pass<n>.fa`` with its ``.agp`` and ``.gff`` (the sequence work on the GPU).  With
+``--fasta_on_gpu`` the contig FASTA is parsed on the GPU into the sequence store instead of line by line in Python.  BESST's path
 search (PROWithinScaf / PROBetweenScaf) stays with BESST - see INTEGRATION.md for plugging these calls into runBESST.
 
 Several GPUs of one node: launch the same command line under torchrun, one process per GPU -
@@ -69,6 +70,12 @@ def build_parser():
                     help='per pass: linearise the graph, chain the paths into scaffolds (MakeScaffolds.Algorithm without '
                          'path extension) and write Scaffolds-pass<n>.fa, info-pass<n>.agp and info-pass<n>.gff; needs -y '
                          'and scoring')
+    ap.add_argument('--fasta_on_gpu', dest='fasta_on_gpu', action='store_true',
+                    help='read the contig FASTA on the GPU: the file goes to HBM as it is and is parsed there into the '
+                         'sequence store (GenerateOutput.SequenceStore.from_fasta); the sequences do not pass through '
+                         'Python strings')
+    ap.add_argument('-filter_contigs', dest='contig_filter_length', type=int, default=None,
+                    help='leave contigs shorter than this out of the run (runBESST -filter_contigs)')
     ap.add_argument('--threads', type=int, default=None, help='BAM inflate threads')
     ap.add_argument('--linearize', action='store_true',
                     help="also run steps 1-4 of MakeScaffolds.Algorithm on a copy of G (isolated scaffolds, "
@@ -179,12 +186,21 @@ def _run(args, rank):
     param.output_directory = out
     param.first_lib = True
     Information = param.information_file = open(os.path.join(out, 'Statistics.txt') if lead else os.devnull, 'w')
-    C_dict = read_fasta(args.contigfile) if lead else {}
+    fasta_on_gpu, filter_length = args.fasta_on_gpu, args.contig_filter_length
+    if fasta_on_gpu:
+        # file bytes -> HBM -> the store; C_dict holds handles into it (the filtered contigs stay in the pool, unused)
+        store = GO.SequenceStore.from_fasta(args.contigfile) if lead else None
+        C_dict = store.contig_dict(filter_length, Information) if lead else {}
+    else:
+        C_dict = read_fasta(args.contigfile) if lead else {}
+        if lead and filter_length is not None:
+            GO.filter_contigs(C_dict, filter_length, Information)
     if lead:
         print('Number of initial contigs:', len(C_dict))
     Contigs, Scaffolds, small_contigs, small_scaffolds = {}, {}, {}, {}
-    # the sequences go to the GPU once, before CreateGraph.PE drops repeats and low-coverage contigs from its dicts
-    store = GO.SequenceStore(list(C_dict), list(C_dict.values())) if args.scaffolds and lead else None
+    if not fasta_on_gpu:
+        # the sequences go to the GPU once, before CreateGraph.PE drops repeats and low-coverage contigs from its dicts
+        store = GO.SequenceStore(list(C_dict), list(C_dict.values())) if args.scaffolds and lead else None
     for i, bam in enumerate(args.bamfiles):
         param.pass_number = i + 1
         param.bamfile = bam

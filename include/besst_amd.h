@@ -37,7 +37,8 @@ extern "C" {
 /* 1: rounds 1-4.  2: + the sharded-scan and BAM-slice entry points of round 5 and the log-normal scoring entry points of
  * round 6 (additions only: a caller built against 1 keeps working).  3: besst_lib_params grew by `mate_bits` (a caller
  * built against 2 passes a shorter struct: recompile), + besst_dev_mate_bits.  Added since without a new version
- * (additions only): the scaffold-output entry points besst_{dev,host}_seq_overlaps / besst_{dev,host}_emit_scaffolds. */
+ * (additions only): the scaffold-output entry points besst_{dev,host}_seq_overlaps / besst_{dev,host}_emit_scaffolds; the
+ * FASTA reader besst_dev_fasta_workspace_bytes / besst_dev_fasta_scan / besst_dev_fasta_pack. */
 #define BESST_ABI_VERSION 3
 
 /* status codes */
@@ -754,6 +755,35 @@ int besst_host_emit_scaffolds(int device, const uint8_t* pool, int64_t pool_byte
                               int64_t literal_bytes, int64_t n_pieces, const int64_t* src_off, const int64_t* len,
                               const uint8_t* mode, const int64_t* out_off, int64_t begin, int64_t end, uint8_t* out,
                               uint64_t* err);
+
+/* ---- the contig FASTA -> the sequence pool above: ReadInContigseqs (runBESST:45-74) on the bytes of the file ----------
+ * `text`: the whole file in HBM, 16-byte aligned, with BESST_EMIT_PAD readable bytes behind its end.  '\n' and '\r' each
+ * end a line.  A line whose first byte is '>' is a header; its name is the first whitespace-delimited token behind the
+ * '>'.  Every other line is stripped of leading and trailing whitespace (bytes 9-13 and 28-32; interior whitespace
+ * stays) and appended to the current contig.  Text in front of the first header belongs to the first contig; a file
+ * without a header is one contig with an empty name.  Rows are in file order, names may repeat.
+ *
+ * tile_bytes: the text is parsed in tiles of that many bytes; 0 = 16384, else a multiple of 1024 in 1024..65536 (the
+ * same value in all three calls).
+ *   besst_dev_fasta_workspace_bytes   scratch for a text of that size; 0: tile_bytes not accepted
+ *   besst_dev_fasta_scan              leaves in info[0..BESST_FASTA_INFO_WORDS): [0] n_contigs, [1] pool_bytes,
+ *                                     [2] names_bytes, [3] first_error: the smallest file offset of a byte >= 0x80 or of
+ *                                     the '>' of a header without a name (all ones: none), [4] set by _pack, [5] header
+ *                                     lines.  The workspace carries the tile offsets on to _pack.
+ *   besst_dev_fasta_pack              n_contigs, pool_bytes, names_bytes as the scan left them.  pool (16-byte aligned,
+ *                                     padded as above) receives the sequences end to end, ctg_off[n_contigs] /
+ *                                     ctg_len[n_contigs] their place, names the names end to end,
+ *                                     name_off[n_contigs + 1] theirs.  info[4]: the first row of 2^31 bases or more (all
+ *                                     ones: none; its ctg_len is 0).
+ * Like every besst_dev_* call: device memory and stream are the caller's, work is only enqueued. */
+#define BESST_FASTA_INFO_WORDS 6
+size_t besst_dev_fasta_workspace_bytes(int64_t text_bytes, int64_t tile_bytes);
+int besst_dev_fasta_scan(void* stream, const uint8_t* text, int64_t text_bytes, int64_t tile_bytes, void* workspace,
+                         size_t workspace_bytes, int64_t* info);
+int besst_dev_fasta_pack(void* stream, const uint8_t* text, int64_t text_bytes, int64_t tile_bytes, const void* workspace,
+                         size_t workspace_bytes, int64_t* info, int64_t n_contigs, int64_t pool_bytes,
+                         int64_t names_bytes, uint8_t* pool, int64_t* ctg_off, int32_t* ctg_len, uint8_t* names,
+                         int64_t* name_off);
 
 #ifdef __cplusplus
 }
