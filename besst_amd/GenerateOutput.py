@@ -8,7 +8,10 @@ they DELETE the removed contigs from the caller's dicts.
 :class:`SequenceStore` in HBM for the whole run, ``seq_overlap_kernel`` finds the overlaps of the junctions that may
 merge, the host turns placements + overlaps into a piece table with numpy, and ``emit_kernel`` gathers the FASTA bytes
 (copy / reverse-complement / 'N' fill) in chunks that are copied back and written while the next chunk is produced.
-AGP and GFF are plain text from names, positions and gaps.  ``SequenceStore.from_fasta`` fills the store from the contig
+AGP and GFF are plain text from names, positions and gaps: on the host by default, and with ``param.outputs_on_gpu`` formatted
+on the device from flat columns and the store's name pool (csrc/emit_text.hip).  A store with ``batch_fasta`` set also
+writes ``repeats.fa`` / ``low_coverage_contigs.fa`` from the pool with one kernel instead of one fetch per contig.
+``SequenceStore.from_fasta`` fills the store from the contig
 FASTA itself (csrc/fasta.hip: the file's bytes are parsed in HBM by the rules of runBESST:45-74); ``C_dict`` then holds
 :class:`SequenceRef` handles instead of strings.  Like the rest of the package there is no CPU path: without
 the library or a GPU these calls raise :class:`besst_amd._lib.BesstDeviceError`.
@@ -40,7 +43,34 @@ def _forget(cont_obj, Contigs, small_contigs):
         del small_contigs[cont_obj.name]
 
 
+def _write_from_pool(cont_objs, path):
+    """The contigs as wrapped FASTA straight from the sequence pool (csrc/emit_text.hip: wrap_fasta_kernel) if every
+    sequence is a :class:`SequenceRef` of one store that has ``batch_fasta`` set and knows the contig by its name.
+    -> False: nothing was written, the caller's own loop has to."""
+    store, rows = None, []
+    for cont_obj in cont_objs:
+        seq = cont_obj.sequence
+        if not isinstance(seq, SequenceRef) or (store is not None and seq.store is not store):
+            return False
+        store = seq.store
+        if not store.batch_fasta or store.name_of(seq.row) != cont_obj.name:
+            return False
+        rows.append(seq.row)
+    if store is None:
+        return False
+    try:
+        store.name_pool()
+    except UnicodeEncodeError:
+        return False
+    write_wrapped_fasta(store, rows, path)
+    return True
+
+
 def PrintOutRepeats(Repeats, Contigs, output_dest, small_contigs):
+    if output_dest and _write_from_pool(Repeats, output_dest + '/repeats.fa'):
+        for cont_obj in Repeats:
+            _forget(cont_obj, Contigs, small_contigs)
+        return ()
     handle = open(output_dest + '/repeats.fa', 'w') if output_dest else None
     for cont_obj in Repeats:
         if handle:
@@ -66,6 +96,10 @@ def repeat_contigs_logger(Repeats, Contigs, output_dest, small_contigs, param):
 
 
 def PrintOut_low_cowerage_contigs(low_coverage_contigs, Contigs, output_dest, small_contigs):
+    if output_dest and _write_from_pool(low_coverage_contigs, output_dest + '/low_coverage_contigs.fa'):
+        for cont_obj in low_coverage_contigs:
+            _forget(cont_obj, Contigs, small_contigs)
+        return ()
     handle = open(output_dest + '/low_coverage_contigs.fa', 'w') if output_dest else None
     for cont_obj in low_coverage_contigs:
         if handle:
@@ -90,6 +124,14 @@ PIECE_COPY, PIECE_REVCOMP, PIECE_FILL_N, PIECE_LITERAL = 0, 1, 2, 3
 MIN_MERGE_OVERLAP = 20                   # reference :140
 CHUNK_BYTES = 256 << 20                  # PrintOutput produces the FASTA in chunks of this size
 NO_ERROR = 0xFFFFFFFFFFFFFFFF
+TEXT_THREADS = 256                       # include/besst_amd.h: BESST_TEXT_THREADS (contigs per workgroup, flags / measure)
+TEXT_SCAN_CHUNK = 4096                   # include/besst_amd.h: BESST_TEXT_SCAN_CHUNK (entries per turn of the scans)
+TEXT_TILE_BYTES = 16384                  # include/besst_amd.h: BESST_TEXT_TILE_BYTES (file bytes per workgroup, AGP / GFF)
+WRAP_TILE_BYTES = 16384                  # include/besst_amd.h: BESST_WRAP_TILE_BYTES (file bytes per workgroup, wrapped FASTA)
+TEXT_AGP, TEXT_GFF = 0, 1
+TEXT_INFO_WORDS = 3                      # include/besst_amd.h: BESST_TEXT_INFO_WORDS
+TEXT_LIMIT = 1 << 62                     # positions and lengths of this magnitude or more are left to the host writer
+FASTA_LINE = 60                          # bases per line of repeats.fa / low_coverage_contigs.fa
 last_timings = {}                        # PrintOutput's wall-time split of its latest call (seconds)
 
 
@@ -156,10 +198,14 @@ def _padded_upload(torch, dev, host_bytes):
 
 class SequenceStore(object):
     """The contig sequences of a run in HBM: uploaded once, read by every pass's output (only placements change between
-    libraries).  One byte per base - case and IUPAC codes survive."""
+    libraries).  One byte per base - case and IUPAC codes survive.
+
+    ``batch_fasta``: PrintOutRepeats / PrintOut_low_cowerage_contigs write their files from the pool in one go."""
+    batch_fasta = False
+    _names = _name_off = _name_at = None
 
     def __init__(self, names, sequences, device=0):
-        names = list(names)
+        names = self._name_list = list(names)
         pool, self.offsets, self.lengths = pack_sequences(sequences)
         if len(names) != len(self.offsets):
             raise ValueError('need one name per sequence')
@@ -192,10 +238,37 @@ class SequenceStore(object):
         self._pool, self.pool_ptr, self.pool_bytes = parsed['pool'], parsed['pool'].data_ptr() + EMIT_PAD, parsed['pool_bytes']
         self._off, self._len = parsed['ctg_off'], parsed['ctg_len']
         self.offsets, self.lengths = self._off.cpu().numpy(), self._len.cpu().numpy()
-        blob, at = parsed['names'].cpu().numpy().tobytes().decode('ascii'), parsed['name_off'].cpu().numpy().tolist()
+        self._names, self._name_off = parsed['names'], parsed['name_off']
+        self._name_at = self._name_off.cpu().numpy()
+        blob, at = self._names.cpu().numpy().tobytes().decode('ascii'), self._name_at.tolist()
         self.names = [blob[a:b] for a, b in zip(at[:-1], at[1:])]
         self.index = {name: i for i, name in enumerate(self.names)}
         return self
+
+    def name_of(self, row):
+        names = getattr(self, 'names', None)
+        return (self._name_list if names is None else names)[row]
+
+    def set_names(self, names):
+        """Other names for the rows (PrintOutput's own store: the contig names of F); the pool is built on demand."""
+        self._name_list = list(names)
+        self._names = self._name_off = self._name_at = None
+
+    def name_pool(self):
+        """The names of the rows end to end on the device -> (uint8 tensor, int64 offsets tensor of len(self) + 1
+        entries, the same offsets as numpy).  A from_fasta store keeps what the parser left; a store built from Python
+        strings uploads the blob at the first call.  UnicodeEncodeError: a name is not ASCII."""
+        if self._names is None:
+            import torch
+            parts = [str(n).encode('ascii') for n in self._name_list]
+            at = np.zeros(len(parts) + 1, dtype=np.int64)
+            np.cumsum(np.fromiter((len(b) for b in parts), dtype=np.int64, count=len(parts)), out=at[1:])
+            blob = np.frombuffer(b''.join(parts) or b'\0', dtype=np.uint8)
+            with warnings.catch_warnings():                      # a read-only view of a bytes object: it is only read
+                warnings.simplefilter('ignore', UserWarning)
+                self._names = torch.from_numpy(blob).to(self.device)
+            self._name_off, self._name_at = torch.from_numpy(at).to(self.device), at
+        return self._names, self._name_off, self._name_at
 
     def fetch(self, row):
         """The bytes of contig ``row``, copied back from the pool."""
@@ -224,7 +297,7 @@ class SequenceStore(object):
         return int(self._pool[EMIT_PAD + int(pool_offset)].item())
 
     def close(self):
-        self._pool = self._off = self._len = None
+        self._pool = self._off = self._len = self._names = self._name_off = None
         self.pool_ptr = None
 
     def __enter__(self):
@@ -380,13 +453,15 @@ class ScaffoldLayout(object):
         self.scaffolds = [sorted(scaf, key=lambda t: t[2]) for scaf in reversed(F)]
         self.names = ['scaffold_' + str(k + 1) + '_uid_' + str(unique_id) for k in range(len(self.scaffolds))]
         two_sigma = 2 * param.std_dev_ins_size
-        row, fwd, first, sep_n, fill, cand = [], [], [], [], [], []
+        row, fwd, first, sep_n, fill, cand, pos, length = [], [], [], [], [], [], [], []
         for scaf in self.scaffolds:
             prev = None
             for t in scaf:
                 row.append(len(row) if index is None else index[t[0]])
                 fwd.append(bool(t[1]))
                 first.append(prev is None)
+                pos.append(t[2])
+                length.append(t[3])
                 if prev is None:
                     sep_n.append(False); fill.append(0); cand.append(False)
                 else:
@@ -401,8 +476,40 @@ class ScaffoldLayout(object):
         self.sep_n = np.asarray(sep_n, dtype=bool)
         self.fill = np.asarray(fill, dtype=np.int64)
         self.cand = np.flatnonzero(np.asarray(cand, dtype=bool))       # flat index of the RIGHT contig of every candidate
+        self.unique_id = unique_id
+        self._pos, self._length = pos, length                          # as given: text_columns() looks at them
         self.off = np.asarray(offsets, dtype=np.int64)[self.row] if len(row) else np.zeros(0, np.int64)
         self.len = np.asarray(lengths, dtype=np.int64)[self.row] if len(row) else np.zeros(0, np.int64)
+
+    def text_columns(self):
+        """The columns the device formats AGP and GFF from (csrc/emit_text.hip), all in output order: ``pos`` / ``len``
+        int64, ``scaffold`` (int32 ordinal of every contig's scaffold), ``scaffold_start`` (int64 first contig of every
+        scaffold) and ``gap`` (bool: the contig has a gap line in front of it).  None where the device cannot stand in for
+        str(): a position or length that is not an integer or of magnitude 2^62 or more, a ``unique_id`` that is no int64."""
+        uid = self.unique_id
+        if isinstance(uid, bool) or not isinstance(uid, (int, np.integer)) or not -(1 << 63) <= int(uid) < 1 << 63:
+            return None
+        cols = []
+        for values in (self._pos, self._length):
+            a = np.asarray(values) if len(values) else np.zeros(0, dtype=np.int64)
+            if a.dtype.kind not in 'iu' or a.ndim != 1:         # floats, bools, objects (Python ints past 64 bits)
+                return None
+            if a.dtype.kind == 'u':
+                if a.size and int(a.max()) >= TEXT_LIMIT:
+                    return None
+            elif a.size and (int(a.max()) >= TEXT_LIMIT or int(a.min()) <= -TEXT_LIMIT):
+                return None
+            cols.append(a.astype(np.int64))
+        pos, length = cols
+        sizes = np.fromiter((len(scaf) for scaf in self.scaffolds), dtype=np.int64, count=len(self.scaffolds))
+        start = np.zeros(len(sizes), dtype=np.int64)
+        if len(sizes) > 1:
+            np.cumsum(sizes[:-1], out=start[1:])
+        scaffold = np.repeat(np.arange(len(sizes), dtype=np.int32), sizes)
+        gap = np.zeros(len(pos), dtype=bool)
+        if len(pos) > 1:
+            gap[1:] = ~self.first[1:] & (pos[1:] > pos[:-1] + length[:-1])
+        return dict(pos=pos, len=length, scaffold=scaffold, scaffold_start=start, gap=gap)
 
     def candidates(self):
         """-> (left row, right row, forward bits) of the junctions whose overlap has to be computed."""
@@ -485,6 +592,8 @@ class _Emitter(object):
         torch, dev = self.torch, self.dev
         self.lib = _lib.load()
         self.layout = lay = ScaffoldLayout(F, param, unique_id, store.offsets, store.lengths, index)
+        if self.own_store and getattr(param, 'outputs_on_gpu', False):
+            store.set_names([t[0] for t in ordered])             # the device text takes the names from the store
         t1 = time.time()
         # overlaps of the candidate junctions
         left, right, forward = lay.candidates()
@@ -621,6 +730,165 @@ def _write_fasta_chunks(em, path, chunk_bytes):
     return t_kernel, t_copy, t_write
 
 
+class _TextEmitter(object):
+    """AGP and GFF of a layout on the device (csrc/emit_text.hip): columns uploaded, lines measured, byte ranges of either
+    file on request.  ``make`` -> None where the host writer has to do the work."""
+
+    @classmethod
+    def make(cls, em):
+        cols = em.layout.text_columns()
+        if cols is None:
+            return None
+        try:
+            pool = em.store.name_pool()
+        except UnicodeEncodeError:
+            return None
+        return cls(em, cols, pool)
+
+    def __init__(self, em, cols, pool):
+        t0 = time.time()
+        torch, dev, lay = em.torch, em.dev, em.layout
+        self.torch, self.dev, self.lib = torch, dev, em.lib
+        names, name_off, name_at = pool
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        self._keep = [up(cols['pos']), up(cols['len']), up(lay.row), up(lay.fwd.astype(np.uint8)), up(cols['scaffold']),
+                      up(cols['scaffold_start']), names, name_off]
+        n = len(lay.row)
+        ptrs = [t.data_ptr() if t.numel() else None for t in self._keep]
+        self.cols = _lib.TextColumns(n, len(lay.scaffolds), int(lay.unique_id), len(name_at) - 1, int(name_at[-1]), *ptrs)
+        p = _C.c_void_p
+        with torch.cuda.device(dev):
+            self.ws_bytes = self.lib.besst_dev_text_workspace_bytes(n)
+            if not self.ws_bytes:
+                raise BesstDeviceError('besst_dev_text_workspace_bytes: %d contigs are out of range' % n)
+            self._ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+            self._info = torch.empty(TEXT_INFO_WORDS, dtype=torch.int64, device=dev)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            stream = torch.cuda.current_stream(dev)
+            ev[0].record(stream)
+            _lib.check(self.lib.besst_dev_text_measure(p(stream.cuda_stream), _C.byref(self.cols), p(self._ws.data_ptr()),
+                                                       self.ws_bytes, p(self._info.data_ptr())), 'besst_dev_text_measure')
+            ev[1].record(stream)
+            info = self._info.cpu().numpy().view(np.uint64)
+        self.totals = (int(info[TEXT_AGP]), int(info[TEXT_GFF]))
+        self._check(int(info[2]))
+        self.measure_seconds = ev[0].elapsed_time(ev[1]) * 1e-3
+        self.prep_seconds = time.time() - t0 - self.measure_seconds
+
+    @staticmethod
+    def _check(bad):
+        if bad != NO_ERROR:
+            raise BesstDeviceError('besst_dev_text: contig %d of the layout names a row, a name or a scaffold outside its '
+                                   'table' % bad)
+
+    def emit(self, which, begin, end, out, stream=None):
+        """Enqueue bytes [begin, end) of the AGP (TEXT_AGP) or GFF (TEXT_GFF) file into ``out`` (uint8, 16-byte aligned)."""
+        if stream is None:
+            stream = self.torch.cuda.current_stream(self.dev)
+        p = _C.c_void_p
+        _lib.check(self.lib.besst_dev_text_emit(p(stream.cuda_stream), _C.byref(self.cols), p(self._ws.data_ptr()),
+                                                self.ws_bytes, which, int(begin), int(end), p(out.data_ptr()),
+                                                p(self._info.data_ptr())), 'besst_dev_text_emit')
+
+    def file(self, which):
+        return _ByteSource(self.torch, self.dev, self.totals[which], lambda b, e, out, stream: self.emit(which, b, e, out, stream))
+
+    def finish(self):
+        self.torch.cuda.synchronize(self.dev)
+        self._check(int(self._info.cpu().numpy().view(np.uint64)[2]))
+
+    def close(self):
+        self._keep = self._ws = self._info = self.cols = None
+
+
+class _ByteSource(object):
+    """What _write_fasta_chunks asks of a file that is produced on the device: its size and byte ranges of it."""
+
+    def __init__(self, torch, dev, total, emit):
+        self.torch, self.dev, self.total, self.emit = torch, dev, total, emit
+
+
+def text_bytes(F, param, store=None, unique_id=None, ranges=None):
+    """(AGP, GFF) as PrintOutput writes them with ``param.outputs_on_gpu``, as bytes; with ``ranges`` (a list of (begin,
+    end)) the bytes of those ranges of each file, in a list per file.  None: the layout is left to the host writer."""
+    em = _Emitter(F, param, store, unique_id)
+    try:
+        text = _TextEmitter.make(em)
+        if text is None:
+            return None
+        torch = em.torch
+        out = []
+        with torch.cuda.device(em.dev):
+            for which in (TEXT_AGP, TEXT_GFF):
+                total, got = text.totals[which], []
+                for begin, end in ([(0, total)] if ranges is None else ranges):
+                    buf = torch.empty(max(16, (end - begin + 15) // 16 * 16), dtype=torch.uint8, device=em.dev)
+                    text.emit(which, begin, end, buf)
+                    got.append(buf[:end - begin].cpu().numpy().tobytes())
+                out.append(got[0] if ranges is None else got)
+        text.finish()
+        text.close()
+        return tuple(out)
+    finally:
+        em.close()
+
+
+def wrapped_fasta_source(store, rows):
+    """The wrapped FASTA ('>' name, lines of FASTA_LINE bases) of the store's ``rows``, in that order, as a device byte
+    source -> (_ByteSource, check): ``check()`` after the last range raises if a record did not fit its table."""
+    torch, dev = _torch_device(store.device.index)
+    lib = _lib.load()
+    names, name_off, name_at = store.name_pool()
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    if len(rows) and (int(rows.min()) < 0 or int(rows.max()) >= len(store)):
+        raise ValueError('a row outside the sequence store')
+    seq_len = np.asarray(store.lengths, dtype=np.int64)[rows]
+    size = 2 + (name_at[1:] - name_at[:-1])[rows] + seq_len + (seq_len + FASTA_LINE - 1) // FASTA_LINE
+    rec_off = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum(size, out=rec_off[1:])
+    d_rows, d_off = torch.from_numpy(rows).to(dev), torch.from_numpy(rec_off).to(dev)
+    err = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    p = _C.c_void_p
+
+    def emit(begin, end, out, stream=None):
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        _lib.check(lib.besst_dev_wrap_fasta(
+            p(stream.cuda_stream), p(store.pool_ptr), store.pool_bytes, len(store), p(store._off.data_ptr()),
+            p(store._len.data_ptr()), p(names.data_ptr()), int(name_at[-1]), p(name_off.data_ptr()), len(rows),
+            p(d_rows.data_ptr()), p(d_off.data_ptr()), int(begin), int(end), p(out.data_ptr()), p(err.data_ptr())),
+            'besst_dev_wrap_fasta')
+
+    def check():
+        bad = int(err.cpu().numpy().view(np.uint64)[0])
+        if bad != NO_ERROR:
+            raise BesstDeviceError('besst_dev_wrap_fasta: record %d does not fit its table' % bad)
+
+    return _ByteSource(torch, dev, int(rec_off[-1]), emit), check
+
+
+def wrapped_fasta_bytes(store, rows, ranges=None):
+    """The wrapped FASTA of ``rows`` as bytes (``ranges``: a list of (begin, end) -> a list of those ranges' bytes)."""
+    src, check = wrapped_fasta_source(store, rows)
+    torch, got = src.torch, []
+    with torch.cuda.device(src.dev):
+        for begin, end in ([(0, src.total)] if ranges is None else ranges):
+            buf = torch.empty(max(16, (end - begin + 15) // 16 * 16), dtype=torch.uint8, device=src.dev)
+            src.emit(begin, end, buf)
+            got.append(buf[:end - begin].cpu().numpy().tobytes())
+    check()
+    return got[0] if ranges is None else got
+
+
+def write_wrapped_fasta(store, rows, path):
+    """``rows`` of the store as wrapped FASTA to ``path``: no contig passes through a Python string.
+    -> seconds spent in (kernels, copies, file writes)"""
+    src, check = wrapped_fasta_source(store, rows)
+    seconds = _write_fasta_chunks(src, path, CHUNK_BYTES)
+    check()
+    return seconds
+
+
 def _write_agp_gff(layout, agp, gff):
     """reference :153-195: coordinates from positions and lengths as given; merges and the one-letter 'n' do not show."""
     print('##gff-version 3', file=gff)
@@ -668,12 +936,29 @@ def PrintOutput(F, Information, output_dest, param, pass_nr, store=None, unique_
             raise
         os.replace(partial, fasta)
         t0 = time.time()
-        with open(pass_dir + '/info-pass' + str(pass_nr) + '.gff', 'w') as gff, \
-                open(pass_dir + '/info-pass' + str(pass_nr) + '.agp', 'w') as agp:
-            _write_agp_gff(em.layout, agp, gff)
+        text = _TextEmitter.make(em) if getattr(param, 'outputs_on_gpu', False) else None
+        split = {}
+        if text is not None:
+            # binary files from the device buffers, through the pinned double buffer of the FASTA
+            try:
+                spent = [_write_fasta_chunks(text.file(which), pass_dir + '/info-pass' + str(pass_nr) + ext, CHUNK_BYTES)
+                         for which, ext in ((TEXT_GFF, '.gff'), (TEXT_AGP, '.agp'))]
+                text.finish()
+                split = dict(text='device', text_prep=text.prep_seconds,
+                             text_kernels=text.measure_seconds + spent[0][0] + spent[1][0],
+                             text_d2h=spent[0][1] + spent[1][1], text_write=spent[0][2] + spent[1][2],
+                             text_bytes=sum(text.totals))
+            finally:
+                text.close()
+        else:
+            with open(pass_dir + '/info-pass' + str(pass_nr) + '.gff', 'w') as gff, \
+                    open(pass_dir + '/info-pass' + str(pass_nr) + '.agp', 'w') as agp:
+                _write_agp_gff(em.layout, agp, gff)
+            if getattr(param, 'outputs_on_gpu', False):
+                split = dict(text='host')
         last_timings.clear()
         last_timings.update(em.seconds, emit_kernels=t_kernel, d2h=t_copy, file_write=t_write,
-                            agp_gff=time.time() - t0, total=time.time() - t_start, fasta_bytes=em.total)
+                            agp_gff=time.time() - t0, total=time.time() - t_start, fasta_bytes=em.total, **split)
     finally:
         em.close()
     return ()

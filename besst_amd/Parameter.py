@@ -18,6 +18,7 @@ _PARAM_DEFAULTS = dict(
     print_scores=None, path_gaps_estimated=0, gap_estimations=None,
     contamination_ratio=0, contamination_mean=None, contamination_stddev=None,
     NO_ILP=None, FASTER_ILP=None,
+    outputs_on_gpu=False,        # not the reference's: AGP / GFF text formatted on the device (GenerateOutput.PrintOutput)
 )
 
 

@@ -66,6 +66,13 @@ class MetricsCounts(C.Structure):
                 ('sample_counter', C.c_int64), ('records_scanned', C.c_int64)]
 
 
+class TextColumns(C.Structure):      # include/besst_amd.h: besst_text_columns
+    _fields_ = [('n_contigs', C.c_int64), ('n_scaffolds', C.c_int64), ('unique_id', C.c_int64), ('n_names', C.c_int64),
+                ('names_bytes', C.c_int64), ('pos', C.c_void_p), ('len', C.c_void_p), ('row', C.c_void_p),
+                ('forward', C.c_void_p), ('scaffold', C.c_void_p), ('scaffold_start', C.c_void_p), ('names', C.c_void_p),
+                ('name_off', C.c_void_p)]
+
+
 def effective_cpus():
     """CPUs this process may actually use: the affinity mask, cut down by the cgroup's CFS quota when there is one
     (cpu.max / cpu.cfs_quota_us).  os.cpu_count() reports the machine - on a container limited to 16 CPUs of a 256-CPU
@@ -220,6 +227,11 @@ _SIGNATURES = {
     'besst_dev_fasta_scan': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
     'besst_dev_fasta_pack': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P, C.c_int64, C.c_int64, C.c_int64,
                                        _P, _P, _P, _P, _P]),
+    'besst_dev_text_workspace_bytes': (C.c_size_t, [C.c_int64]),
+    'besst_dev_text_measure': (C.c_int, [_P, C.POINTER(TextColumns), _P, C.c_size_t, _P]),
+    'besst_dev_text_emit': (C.c_int, [_P, C.POINTER(TextColumns), _P, C.c_size_t, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
+    'besst_dev_wrap_fasta': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P,
+                                       C.c_int64, C.c_int64, _P, _P]),
 }
 
 _lib = None

@@ -7,7 +7,11 @@ Flag names and defaults follow runBESST:254-402 for everything the hot path read
 ``CreateGraph.PE`` and writes Statistics.txt plus the scored edge tables of G and G' as TSV.  With ``--scaffolds -y`` it
 goes on like runBESST's loop without path extension: the graph is linearised, the paths become scaffolds, and every pass
 writes ``pass<n>/Scaffolds-pass<n>.fa`` with its ``.agp`` and ``.gff`` (the sequence work on the GPU).  With
-``--fasta_on_gpu`` the contig FASTA is parsed on the GPU into the sequence store instead of line by line in Python.  BESST's path
+``--fasta_on_gpu`` the contig FASTA is parsed on the GPU into the sequence store instead of line by line in Python.  With
+``--outputs_on_gpu`` the AGP and GFF text is formatted on the GPU too, and ``repeats.fa`` / ``low_coverage_contigs.fa`` are
+written from the sequence store in one go where the contigs live there (``--fasta_on_gpu``).  ``--final_fasta`` leaves the
+directory as runBESST does without --separate_repeats: ``pass<n>/Scaffolds_pass<n>.fa`` holds the scaffolds followed by
+the repeats, ``Scaffolds-pass<n>.fa`` and, after the last pass, ``repeats.fa`` are gone.  BESST's path
 search (PROWithinScaf / PROBetweenScaf) stays with BESST - see INTEGRATION.md for plugging these calls into runBESST.
 
 Several GPUs of one node: launch the same command line under torchrun, one process per GPU -
@@ -21,6 +25,7 @@ from __future__ import print_function
 
 import argparse
 import os
+import shutil
 import sys
 from time import time
 
@@ -74,6 +79,13 @@ def build_parser():
                     help='read the contig FASTA on the GPU: the file goes to HBM as it is and is parsed there into the '
                          'sequence store (GenerateOutput.SequenceStore.from_fasta); the sequences do not pass through '
                          'Python strings')
+    ap.add_argument('--outputs_on_gpu', dest='outputs_on_gpu', action='store_true',
+                    help='format info-pass<n>.agp / .gff on the GPU, and write repeats.fa / low_coverage_contigs.fa '
+                         'from the sequence store in one go where the contigs live there (--fasta_on_gpu)')
+    ap.add_argument('--final_fasta', dest='final_fasta', action='store_true',
+                    help="leave runBESST's final files: pass<n>/Scaffolds_pass<n>.fa = the scaffolds followed by "
+                         'repeats.fa (Scaffolds-pass<n>.fa is renamed, repeats.fa removed after the last pass); needs '
+                         '--scaffolds')
     ap.add_argument('-filter_contigs', dest='contig_filter_length', type=int, default=None,
                     help='leave contigs shorter than this out of the run (runBESST -filter_contigs)')
     ap.add_argument('--threads', type=int, default=None, help='BAM inflate threads')
@@ -125,6 +137,19 @@ def write_scaffolds(G, G_prime, Contigs, small_contigs, Scaffolds, small_scaffol
           file=Information)
 
 
+def finish_pass_fasta(out, pass_nr):
+    """runBESST:220-226: Scaffolds-pass<n>.fa becomes Scaffolds_pass<n>.fa, followed by repeats.fa as it stands now (the
+    scaffolds are renamed and the repeats appended: the large file is not copied)."""
+    pass_dir = os.path.join(out, 'pass%d' % pass_nr)
+    final = os.path.join(pass_dir, 'Scaffolds_pass%d.fa' % pass_nr)
+    os.replace(os.path.join(pass_dir, 'Scaffolds-pass%d.fa' % pass_nr), final)
+    repeats = os.path.join(out, 'repeats.fa')
+    if os.path.exists(repeats):
+        with open(final, 'ab') as dst, open(repeats, 'rb') as src:
+            shutil.copyfileobj(src, dst, 16 << 20)
+    return final
+
+
 def join_process_group():
     """Under torchrun (WORLD_SIZE > 1): one rank per GPU over RCCL (backend 'nccl'; BESST_DIST_BACKEND=gloo for several
     ranks on one GPU).  -> (rank, whether this call initialised the group)."""
@@ -157,6 +182,8 @@ def main(argv=None):
     if args.scaffolds and args.no_score:
         sys.exit('--scaffolds cannot be combined with --no_score: without scores BESST skips the linearisation and the '
                  'scaffold step, and its path search, which would do the work instead, is not part of this package')
+    if args.final_fasta and not args.scaffolds:
+        sys.exit('--final_fasta needs --scaffolds: Scaffolds_pass<n>.fa is the scaffold FASTA followed by the repeats')
     if args.max_contig_overlap < 0 or args.max_contig_overlap > GO.MAX_CONTIG_OVERLAP_LIMIT:
         sys.exit('-max_contig_overlap must lie in 0..%d' % GO.MAX_CONTIG_OVERLAP_LIMIT)
     rank, joined = join_process_group()
@@ -183,6 +210,7 @@ def _run(args, rank):
     param.detect_haplotype = False
     param.print_scores = False
     param.max_contig_overlap = args.max_contig_overlap
+    param.outputs_on_gpu = args.outputs_on_gpu
     param.output_directory = out
     param.first_lib = True
     Information = param.information_file = open(os.path.join(out, 'Statistics.txt') if lead else os.devnull, 'w')
@@ -191,6 +219,8 @@ def _run(args, rank):
         # file bytes -> HBM -> the store; C_dict holds handles into it (the filtered contigs stay in the pool, unused)
         store = GO.SequenceStore.from_fasta(args.contigfile) if lead else None
         C_dict = store.contig_dict(filter_length, Information) if lead else {}
+        if lead and args.outputs_on_gpu:
+            store.batch_fasta = True
     else:
         C_dict = read_fasta(args.contigfile) if lead else {}
         if lead and filter_length is not None:
@@ -201,6 +231,8 @@ def _run(args, rank):
     if not fasta_on_gpu:
         # the sequences go to the GPU once, before CreateGraph.PE drops repeats and low-coverage contigs from its dicts
         store = GO.SequenceStore(list(C_dict), list(C_dict.values())) if args.scaffolds and lead else None
+        if store is not None and args.outputs_on_gpu:
+            store.batch_fasta = True
     for i, bam in enumerate(args.bamfiles):
         param.pass_number = i + 1
         param.bamfile = bam
@@ -245,9 +277,13 @@ def _run(args, rank):
             write_edges(os.path.join(pass_dir, 'edges_G_linear.tsv'), L)
         if args.scaffolds:
             write_scaffolds(G, G_prime, Contigs, small_contigs, Scaffolds, small_scaffolds, Information, param, i + 1, store)
+            if args.final_fasta:
+                finish_pass_fasta(out, i + 1)
         print('pass %d: %d records, G %d link edges, G_prime %d link edges' % (
             i + 1, len(records), sum(1 for u, v in G.edges() if G[u][v]['nr_links'] is not None),
             sum(1 for u, v in G_prime.edges() if G_prime[u][v]['nr_links'] is not None)))
+    if lead and args.final_fasta and os.path.exists(os.path.join(out, 'repeats.fa')):
+        os.remove(os.path.join(out, 'repeats.fa'))               # runBESST:233-234
     if store is not None:
         store.close()
     Information.close()

@@ -38,7 +38,8 @@ extern "C" {
  * round 6 (additions only: a caller built against 1 keeps working).  3: besst_lib_params grew by `mate_bits` (a caller
  * built against 2 passes a shorter struct: recompile), + besst_dev_mate_bits.  Added since without a new version
  * (additions only): the scaffold-output entry points besst_{dev,host}_seq_overlaps / besst_{dev,host}_emit_scaffolds; the
- * FASTA reader besst_dev_fasta_workspace_bytes / besst_dev_fasta_scan / besst_dev_fasta_pack. */
+ * FASTA reader besst_dev_fasta_workspace_bytes / besst_dev_fasta_scan / besst_dev_fasta_pack; the text of the output stage
+ * besst_dev_text_workspace_bytes / besst_dev_text_measure / besst_dev_text_emit / besst_dev_wrap_fasta. */
 #define BESST_ABI_VERSION 3
 
 /* status codes */
@@ -784,6 +785,59 @@ int besst_dev_fasta_pack(void* stream, const uint8_t* text, int64_t text_bytes, 
                          size_t workspace_bytes, int64_t* info, int64_t n_contigs, int64_t pool_bytes,
                          int64_t names_bytes, uint8_t* pool, int64_t* ctg_off, int32_t* ctg_len, uint8_t* names,
                          int64_t* name_off);
+
+/* ---- the text of the output stage: info-pass<n>.agp / .gff (GenerateOutput.py:156-195, 208-221) and the wrapped FASTA of
+ * repeats.fa / low_coverage_contigs.fa (:47-53, 68-74), formatted on the device ------------------------------------------
+ * besst_text_columns: the contigs of all scaffolds in output order (scaffolds as reversed(F), each sorted by position).
+ * Contig i lies at pos[i] with len[i] bases, is written as stored where forward[i] is not 0, belongs to scaffold
+ * scaffold[i] (0-based ordinal; the file says ordinal + 1), whose first contig is scaffold_start[ordinal], and is named
+ * names[name_off[row[i]] .. name_off[row[i] + 1]) (name_off: n_names + 1 entries).  Scaffold k is named
+ * scaffold_<k + 1>_uid_<unique_id>.  Per contig: a gap line if it is not the first of its scaffold and
+ * pos[i] - (pos[i-1] + len[i-1]) > 0, then its own line; the component number counts both and starts at 1 per scaffold.
+ * Numbers are signed decimals; |pos|, |len| below 2^62.
+ *   besst_dev_text_workspace_bytes   scratch for n_contigs contigs (0: n_contigs out of range); 256-byte aligned
+ *   besst_dev_text_measure           fills the workspace (component numbers, the offsets of every contig's lines in both
+ *                                    files) and info[0..BESST_TEXT_INFO_WORDS): [0] bytes of the AGP file, [1] of the GFF
+ *                                    file, [2] the first contig whose row, name range or scaffold is invalid (all ones:
+ *                                    none; its name is written empty)
+ *   besst_dev_text_emit              bytes [begin, end) of file `which` to out[0 .. end - begin) (16-byte aligned), from
+ *                                    the same columns and the workspace as measured; bytes past the file's end are 0
+ * The kernels work in units that tests aim at: BESST_TEXT_THREADS contigs per workgroup of the flag and measure passes,
+ * BESST_TEXT_SCAN_CHUNK entries per turn of the scans, BESST_TEXT_TILE_BYTES file bytes per workgroup of the emission.
+ *
+ * besst_dev_wrap_fasta: record r is contig rows[r] of the pool above: '>' name '\n', then the sequence in lines of 60
+ * bytes, each followed by '\n' (the last, shorter one too; an empty sequence has the header line only).  rec_off:
+ * n_rows + 1 entries, the exclusive prefix sum of 1 + |name| + 1 + len + ceil(len / 60).  Bytes [begin, end) of that file
+ * go to out (16-byte aligned), BESST_WRAP_TILE_BYTES per workgroup.  err[0]: min r of the records whose row, name, pool
+ * range or size in rec_off is wrong (their bytes come out as '?'); the caller sets it to all ones.  rows may repeat.
+ * Like every besst_dev_* call: device memory and stream are the caller's, work is only enqueued. */
+typedef struct besst_text_columns {
+    int64_t n_contigs, n_scaffolds, unique_id, n_names, names_bytes;
+    const int64_t* pos;
+    const int64_t* len;
+    const int64_t* row;
+    const uint8_t* forward;
+    const int32_t* scaffold;
+    const int64_t* scaffold_start;
+    const uint8_t* names;
+    const int64_t* name_off;
+} besst_text_columns;
+#define BESST_TEXT_AGP 0
+#define BESST_TEXT_GFF 1
+#define BESST_TEXT_INFO_WORDS 3
+#define BESST_TEXT_THREADS 256
+#define BESST_TEXT_SCAN_CHUNK 4096
+#define BESST_TEXT_TILE_BYTES 16384
+#define BESST_WRAP_TILE_BYTES 16384
+size_t besst_dev_text_workspace_bytes(int64_t n_contigs);
+int besst_dev_text_measure(void* stream, const besst_text_columns* cols, void* workspace, size_t workspace_bytes,
+                           int64_t* info);
+int besst_dev_text_emit(void* stream, const besst_text_columns* cols, const void* workspace, size_t workspace_bytes,
+                        int32_t which, int64_t begin, int64_t end, uint8_t* out, int64_t* info);
+int besst_dev_wrap_fasta(void* stream, const uint8_t* pool, int64_t pool_bytes, int64_t n_contigs, const int64_t* ctg_off,
+                         const int32_t* ctg_len, const uint8_t* names, int64_t names_bytes, const int64_t* name_off,
+                         int64_t n_rows, const int64_t* rows, const int64_t* rec_off, int64_t begin, int64_t end,
+                         uint8_t* out, uint64_t* err);
 
 #ifdef __cplusplus
 }
