@@ -172,6 +172,7 @@ _SIGNATURES = {
                                    _P, _P, C.c_size_t, _P, C.c_uint64]),
     'besst_dev_reduce_flags': (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                          _P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32]),
+    'besst_dev_reduce_census': (C.c_int, [_P, C.c_int64, C.c_int32, C.c_uint32, _P, C.c_size_t, _P]),
     'besst_dev_reduce_presort': (C.c_int, [C.c_int64, C.c_int32, C.c_uint64, _P, C.c_size_t, C.POINTER(Presort)]),
     'besst_dev_classify_presort': (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P,
                                              C.POINTER(LibParams), C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,

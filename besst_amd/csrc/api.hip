@@ -1476,6 +1476,11 @@ int besst_dev_reduce(void* stream, int64_t capacity, const uint32_t* n_tuples, i
                                   first_map, key_base, 0u);
 }
 
+int besst_dev_reduce_census(void* stream, int64_t capacity, int32_t key_bits, uint32_t flags, const void* workspace,
+                            size_t workspace_bytes, int64_t* h_out) {
+    return reduce_census(static_cast<hipStream_t>(stream), capacity, key_bits, flags, workspace, workspace_bytes, h_out);
+}
+
 static int fill_classify_args(ClassifyArgs& a, int64_t n, const int32_t* tid, const int32_t* mtid, const int32_t* pos,
                               const int32_t* mpos, const uint16_t* flag, const uint8_t* mapq, const uint16_t* qlen,
                               int64_t n_contigs, const void* contig_table, const besst_lib_params* p,

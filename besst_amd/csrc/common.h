@@ -370,6 +370,10 @@ int launch_runs_reduce(hipStream_t s, int64_t cap, const uint32_t* n_tuples, int
                        uint32_t* row_first, uint32_t* row_offset, int32_t* obs_lo, int32_t* obs_hi, uint32_t* n_rows,
                        void* ws, size_t ws_bytes, const uint32_t* first_map, uint64_t key_base);
 void* onesweep_staged_rows(void* ws, int64_t cap);
+// test and diagnosis: the form launch_sort_reduce selects and what the last call left in the workspace (8 host words)
+int reduce_census(hipStream_t s, int64_t cap, int key_bits, uint32_t flags, const void* ws, size_t ws_bytes, int64_t* out);
+bool onesweep_takes_bucket_form(int64_t cap, int key_bits);
+int onesweep_census(int64_t cap, const void* ws, int64_t* counts /* 5 */);
 // chained-scan sort + atomic-free reduction for large streams (onesweep.hip); buf_* = the ping-pong buffers of the
 // sort/reduce workspace
 size_t onesweep_workspace_bytes(int64_t cap);

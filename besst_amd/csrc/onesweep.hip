@@ -30,6 +30,8 @@
 // aligned 8-byte {tag, value} written by ONE relaxed agent-scope store and polled with relaxed agent-scope loads;
 // tag = (phase << 2) | status with phase counted inside the call (never 0), all granules zeroed by the first kernel
 // of the call.  Spins are bounded: a tile that gives up sets the workspace's error word instead of hanging the GPU.
+#include <vector>
+
 #include "common.h"
 
 namespace besst {
@@ -1584,6 +1586,26 @@ bool onesweep_presort_spec(int64_t cap, int key_bits, uint64_t key_base, void* w
 }
 
 void* onesweep_staged_rows(void* ws, int64_t cap) { return os_carve(ws, cap < 1 ? 1 : cap, kOsBits).staged; }
+
+bool onesweep_takes_bucket_form(int64_t cap, int key_bits) { return os_hybrid(cap, key_bits); }
+
+// Test and diagnosis: which kernel finished each top-16-bit bucket in the last bucket-form call on this workspace, read
+// back from what os_bucket_start_kernel / os_bucket_wave_kernel left there and counted on the host.  counts[0..4]:
+// buckets that are empty / done by os_bucket_wave_kernel / by os_bucket_wave_lds_kernel / by os_bucket_sort_kernel in
+// LDS / by os_bucket_sort_kernel in global memory.  The stream must be idle.
+int onesweep_census(int64_t cap, const void* ws, int64_t* counts) {
+    const OsWorkspace w = os_carve(const_cast<void*>(ws), cap, kOsBits);
+    std::vector<uint32_t> start((size_t)kTopBuckets + 1), cls((size_t)kTopBuckets);
+    BESST_HIP_TRY(hipMemcpy(start.data(), w.bucket_start, start.size() * 4, hipMemcpyDeviceToHost));
+    BESST_HIP_TRY(hipMemcpy(cls.data(), w.bucket_class, cls.size() * 4, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 5; ++k) counts[k] = 0;
+    for (int b = 0; b < kTopBuckets; ++b) {
+        const uint32_t n = start[b + 1] - start[b];
+        const int k = n == 0 ? 0 : cls[b] == 0u ? 1 : cls[b] == 1u ? 2 : n <= (uint32_t)kBkCap ? 3 : 4;
+        ++counts[k];
+    }
+    return BESST_OK;
+}
 
 size_t onesweep_workspace_bytes(int64_t cap) {
     if (cap < 1) cap = 1;

@@ -22,6 +22,7 @@
 #include <atomic>
 #include <random>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 
@@ -583,6 +584,9 @@ __device__ __forceinline__ void bitonic_words(uint64_t* k, int np) {          //
 #endif
 constexpr uint32_t kRankCostLimit = BESST_RANK_COST_LIMIT;   // LDS reads per word above which a bucket takes the network
 
+constexpr int kBucketPackedCap = 4096;                    // LDS capacity of the packed configuration (launch_sort_reduce)
+constexpr int bucket_rank_max(int cap) { return cap <= 512 ? cap : 256; }   // largest bucket the plain rank sort takes
+
 template <bool kPacked, int kCap>
 __global__ __launch_bounds__(kBucketThreads) void bucket_sort_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ idx,
                                                           const uint32_t* __restrict__ bucket_start,
@@ -593,7 +597,7 @@ __global__ __launch_bounds__(kBucketThreads) void bucket_sort_kernel(uint64_t* _
                                                           int sub_bits /* key bits below the MSD digit */,
                                                           const unsigned long long* __restrict__ msd_flags,
                                                           unsigned long long nonce) {
-    constexpr int kRank = kCap <= 512 ? kCap : 256;     // largest bucket the plain rank sort takes
+    constexpr int kRank = bucket_rank_max(kCap);
     static_assert(kPacked || kCap <= 512, "unpacked pairs are only sorted in the small-stream configuration");
     static_assert(kBucketThreads == 256 || kCap <= 512, "the group scan of the two-level sort uses one thread per group");
     __shared__ uint64_t s_k[kCap <= 512 ? kCap : 256];   // rank-sort input (buckets up to kRank words)
@@ -1181,13 +1185,24 @@ size_t reduce_workspace_bytes(int64_t cap) {
 }
 
 
+// bits of a stream index below `cap`
+static int index_bits(int64_t cap) {
+    int bits = 1;
+    while (((int64_t)1 << bits) < cap) ++bits;
+    return bits;
+}
+
+// the words of an MSD bucket hold key and stream index: the MSD digit is implied by the bucket, so only the key bits below
+// it have to fit next to the index
+static bool bucket_words_packable(int64_t cap, int key_bits) {
+    return (key_bits > kMsdBits ? key_bits - kMsdBits : 0) + index_bits(cap) <= 64;
+}
+
 // which streams launch_sort_reduce hands to the chained-scan passes (the test of its large-stream branch)
 static bool takes_large_stream_path(int64_t cap, int key_bits) {
     const uint32_t nb_sort = (uint32_t)((cap + kSortTile - 1) / kSortTile);
-    int cap_idx_bits = 1;
-    while (((int64_t)1 << cap_idx_bits) < cap) ++cap_idx_bits;
-    const bool packable = (key_bits > kMsdBits ? key_bits - kMsdBits : 0) + cap_idx_bits <= 64;
-    return !(nb_sort <= (uint32_t)kScanFreeMaxBlocks || (packable && nb_sort <= (uint32_t)kMsdMaxBlocks));
+    return !(nb_sort <= (uint32_t)kScanFreeMaxBlocks ||
+             (bucket_words_packable(cap, key_bits) && nb_sort <= (uint32_t)kMsdMaxBlocks));
 }
 
 bool sort_presort_spec(int64_t cap, int key_bits, uint64_t key_base, void* ws, size_t ws_bytes, PresortSpec* out) {
@@ -1221,11 +1236,9 @@ int launch_sort_reduce(hipStream_t s, int64_t cap, const uint32_t* n_tuples, int
     const uint64_t* kin = keys;
     const uint32_t* iin = nullptr;
     int packed_bits = 0;
-    int cap_idx_bits = 1;
-    while (((int64_t)1 << cap_idx_bits) < cap) ++cap_idx_bits;
-    // the MSD digit is implied by the bucket, so only the key bits below it have to fit next to the index
-    const bool packable = (key_bits > kMsdBits ? key_bits - kMsdBits : 0) + cap_idx_bits <= 64;
-    if (nb_sort <= (uint32_t)kScanFreeMaxBlocks || (packable && nb_sort <= (uint32_t)kMsdMaxBlocks)) {
+    const int cap_idx_bits = index_bits(cap);
+    const bool packable = bucket_words_packable(cap, key_bits);
+    if (!takes_large_stream_path(cap, key_bits)) {
         // one MSD pass on the top 11 significant bits, then every bucket sorts and reduces itself
         const int shift = key_bits > kMsdBits ? key_bits - kMsdBits : 0;
         const DigitSel ds{0, shift, 0, 1u, kMsdBits, key_base};
@@ -1260,7 +1273,7 @@ int launch_sort_reduce(hipStream_t s, int64_t cap, const uint32_t* n_tuples, int
                 hipLaunchKernelGGL((bucket_sort_kernel<false, kBucketLds>), grid, block, 0, s, w.keys[0], w.idx[0],
                                    w.bucket_start, n_tuples, w.big_keys, w.big_idx, w.bucket_rows, 0, shift, mflags, nonce);
             else
-                hipLaunchKernelGGL((bucket_sort_kernel<true, 4096>), grid, block, 0, s, w.keys[0], w.idx[0],
+                hipLaunchKernelGGL((bucket_sort_kernel<true, kBucketPackedCap>), grid, block, 0, s, w.keys[0], w.idx[0],
                                    w.bucket_start, n_tuples, w.big_keys, w.big_idx, w.bucket_rows, packed_bits, shift, mflags, nonce);
         }
         if (packed_bits) {
@@ -1306,6 +1319,46 @@ int launch_sort_reduce(hipStream_t s, int64_t cap, const uint32_t* n_tuples, int
                        row_first, row_offset, obs_lo, obs_hi, first_map, packed_bits);
     BESST_HIP_TRY(hipGetLastError());
     return BESST_OK;
+}
+
+// Test and diagnosis (besst_dev_reduce_census): the form launch_sort_reduce selects for these arguments - by the tests it
+// makes itself - and, for the two forms that finish bucket by bucket, the size classes of the buckets the last call on
+// this workspace left behind, counted on the host.  No kernel; synchronises the stream.
+//   out[0]  0 MSD partition + buckets, 1 run-grouped, 2 chained scan + buckets, 3 chained scan + tile reduction
+//   form 0: out[1..4] buckets of <= 1 word / up to the rank sort's limit / up to the LDS capacity / beyond it
+//           (bucket_sort_kernel's branches; an EMPTY stream partitions nothing and leaves the table of the call before)
+//   form 2: out[1..5] onesweep_census
+int reduce_census(hipStream_t s, int64_t cap, int key_bits, uint32_t flags, const void* ws, size_t ws_bytes, int64_t* out) {
+    BESST_REQUIRE(out != nullptr, "reduce_census: null output");
+    for (int k = 0; k < 8; ++k) out[k] = 0;
+    BESST_REQUIRE(cap >= 1 && cap < ((int64_t)1 << 32), "reduce_census: capacity out of range");
+    BESST_REQUIRE(key_bits >= 1 && key_bits <= 64, "reduce_census: key_bits out of range");
+    const RedWorkspace w = carve(const_cast<void*>(ws), cap);
+    BESST_REQUIRE(ws != nullptr && ws_bytes >= w.total, "reduce_census: workspace too small");
+    BESST_HIP_TRY(hipStreamSynchronize(s));
+    if (!takes_large_stream_path(cap, key_bits)) {
+        out[0] = 0;
+        const bool packed = bucket_words_packable(cap, key_bits);
+        const uint32_t lds = packed ? (uint32_t)kBucketPackedCap : (uint32_t)kBucketLds;
+        const uint32_t rank = (uint32_t)bucket_rank_max((int)lds);
+        std::vector<uint32_t> start((size_t)(1 << kMsdBits) + 1);
+        BESST_HIP_TRY(hipMemcpy(start.data(), w.bucket_start, start.size() * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < (1 << kMsdBits); ++b) {
+            const uint32_t n = start[b + 1] - start[b];
+            ++out[n <= 1u ? 1 : n <= rank ? 2 : n <= lds ? 3 : 4];
+        }
+        return BESST_OK;
+    }
+    if (w.rg_bytes && !(flags & BESST_REDUCE_NO_RUNS)) {
+        out[0] = 1;
+        return BESST_OK;
+    }
+    if (!onesweep_takes_bucket_form(cap, key_bits)) {
+        out[0] = 3;
+        return BESST_OK;
+    }
+    out[0] = 2;
+    return onesweep_census(cap, w.os_ws, out + 1);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -386,6 +386,16 @@ class DeviceGraphBuilder(object):
                 int(n_rows), 'a chained-scan look-back gave up' if int(n_rows) == ROWS_SORT_FAILED else 'run overflow'))
         return int(n_out), int(n_rows)
 
+    def reduce_census(self, capacity=None):
+        """besst_dev_reduce_census for this builder's key range, flags and workspace (a test and diagnosis accessor;
+        synchronises) -> 8 ints: the form a stage-2 call of `capacity` selects, then the bucket classes of the last one."""
+        out = (C.c_int64 * 8)()
+        cap = self.tup_cap if capacity is None else int(capacity)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self.lib.besst_dev_reduce_census(C.c_void_p(stream), cap, self.key_bits, self.sort_flags, _p(self.ws2),
+                                                    self.ws2.numel(), out), 'dev_reduce_census')
+        return [int(v) for v in out]
+
     def read_counters(self):
         raw = self.small.cpu().numpy().tobytes()
         ctr = Counters.from_buffer_copy(raw[:COUNTER_BYTES])

@@ -426,13 +426,17 @@ int besst_dev_candidate_density(void* stream, int64_t n, const int32_t* tid, con
 
 /* Stage 2: sort of the tuples by (key, position in the stream) - observably a stable sort by key - and segmented
  * reduction into edge rows (up to 4 M tuples: one MSD partition + per-bucket sort and reduction; beyond, up to 2^30:
- * run-grouped - every 1024 consecutive tuples are grouped into runs of equal keys and the runs are sorted - or, with
+ * run-grouped - every 512 consecutive tuples are grouped into runs of equal keys and the runs are sorted - or, with
  * BESST_REDUCE_NO_RUNS, chained-scan radix passes over the tuples).  *n_rows may come back as BESST_ROWS_*.
  *   n_tuples  uint32 device: number of valid tuples in keys/payload (<= capacity)
  *   key_base  a lower bound of every key (0 is always valid).  Scaffold ids keep growing across passes
  *             (param.scaffold_indexer, MakeScaffolds.py:276), so from the second library on all keys share a long
  *             common prefix; with key_base = ((2 * min scaffold id) << node_bits) << 1 the sort works on key - key_base
  *   key_bits  number of significant bits of key - key_base (2 * node_bits + 1 with key_base 0)
+ * Payload: obs1 >= 0 in the low 32 bits, obs2 in bits 32..61 (30 bits), the graph mask in the top 2 (a row's mask is
+ *   its first tuple's).  obs1 + obs2 is formed in 32 bits and must stay below 2^32; the tuples the record loop emits
+ *   have obs1 + obs2 < 2^30 (ins_size_threshold is refused from 2^30 on).  Squares and a row's sums are 64-bit: sum obs
+ *   and sum obs^2 are exact while they fit 63 bits (row_sum / row_sum_sq are int64).
  * Outputs (capacity entries each): row_* arrays, obs_lo/obs_hi grouped by row, n_rows (uint32). */
 int besst_dev_reduce(void* stream, int64_t capacity, const uint32_t* n_tuples, int32_t key_bits,
                      const uint64_t* keys, const uint64_t* payload, uint64_t* row_key,
@@ -447,6 +451,19 @@ int besst_dev_reduce_flags(void* stream, int64_t capacity, const uint32_t* n_tup
                            uint32_t* row_first, uint32_t* row_offset, int32_t* obs_lo, int32_t* obs_hi,
                            uint32_t* n_rows, void* workspace, size_t workspace_bytes, const uint32_t* first_map,
                            uint64_t key_base, uint32_t flags);
+
+/* A test and diagnosis accessor, not part of a graph build: what besst_dev_reduce_flags with this capacity / key_bits /
+ * flags selects, and what the last such call left in `workspace`.  SYNCHRONISES the stream, copies the bucket tables
+ * out of the workspace and counts on the host; launches no kernel.  h_out: 8 host words.
+ *   h_out[0]  the form: 0 = MSD partition + buckets, 1 = run-grouped, 2 = chained scan + buckets,
+ *             3 = chained scan + tile reduction (the launcher's own tests, not a copy of them)
+ *   form 2:   h_out[1..5] = top-16-bit buckets that were empty / finished by the wave kernel / by the wave kernel's digit
+ *             passes / by a workgroup in LDS (<= 4096 words) / by a workgroup in global memory
+ *   form 0:   h_out[1..4] = 11-bit buckets of <= 1, 2..256, 257..4096 and > 4096 words (an empty stream partitions
+ *             nothing: the counts are then those of the call before)
+ *   other forms and the remaining words: 0 */
+int besst_dev_reduce_census(void* stream, int64_t capacity, int32_t key_bits, uint32_t flags, const void* workspace,
+                            size_t workspace_bytes, int64_t* h_out);
 
 /* Stage 1 + 2 on buffers that stay allocated (a resident builder): the large-stream form of stage 2 starts with a
  * histogram read of the whole key stream, which stage 1 can take on its way out (it has every key in registers when it

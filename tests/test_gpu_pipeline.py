@@ -4,6 +4,7 @@ import pytest
 from oracle import py_oracle as O
 from tests import golden_util as GU
 from tests import gpu_util as DU
+from tests.test_gpu_runs import assert_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -52,6 +53,14 @@ def test_record_path_follows_candidate_density(monkeypatch):
         assert abs(gb.candidate_share - share) < 0.02
 
 
+# (sort_flags after read_sizes(), form of besst_dev_reduce_census) of the streams beyond 4 M tuples below, as observed: random
+# keys overflow the run buffers and are served by the chained-scan forms (2: + buckets, 3: + tile reduction); the 3- and
+# 5-bit keys cluster by their nature and stay in the run-grouped form (1)
+LARGE_SYNTHETIC_FORMS = {(5_000_000, 41): (1, 2), (6_000_000, 37): (1, 2), (5_000_000, 45): (1, 3), (4_300_000, 3): (0, 1),
+                         (8192 * 600 + 1, 37): (1, 2), (4096 * 1100, 5): (0, 1), (4_500_000, 39): (1, 2),
+                         (4_400_000, 33): (1, 2)}
+
+
 @pytest.mark.parametrize('n,key_bits,hub', [(50_000, 31, 20_000), (3_000, 9, 0), (200_000, 41, 700), (1, 31, 0),
                                             (600_000, 33, 100_000), (700_000, 41, 0), (1_000_000, 41, 3_000),
                                             (1_000_000, 45, 0), (1_500_000, 41, 0), (200_000, 57, 500),
@@ -64,9 +73,12 @@ def test_sort_reduce_on_synthetic_tuples(n, key_bits, hub):
     than one digit, the small-stream MSD path (scan-free table, rank sort), the mid-size MSD path (row-scanned table,
     rank sort / LDS bitonic / global bitonic buckets), 57- and 55-bit keys that only pack because the MSD digit is implied by the bucket, a
     stream whose words do not fit 64 bits even so (59-bit keys: LSD passes with index arrays), and streams beyond 4 M
-    tuples (chained-scan radix passes + atomic-free row reduction, csrc/onesweep.hip): packed words, a hub row of
-    150 000 tuples, 45-bit keys that travel with a separate index array, 3- and 5-bit keys whose few rows run
-    across hundreds of reduce tiles, and streams that end one tuple into / exactly at a tile.  Packed keys of four digits
+    tuples.  Those first take the run-grouped form (csrc/runs.hip); random keys overflow its run buffers, read_sizes()
+    repeats the call and the chained-scan radix passes (csrc/onesweep.hip) serve them (LARGE_SYNTHETIC_FORMS pins which
+    form each stream ends in): packed words, a hub row of 150 000 tuples, 45-bit keys that travel with a separate index
+    array and end in the tile reduction, and a stream that ends one tuple into a tile.  The 3- and 5-bit keys, whose few
+    rows run across hundreds of tiles, cluster whatever their order: they stay in the run-grouped form (rows that run
+    across reduce tiles of the chained-scan form are designed in tests/test_gpu_sort_classes.py).  Packed keys of four digits
     or more take two chained-scan passes on the top 16 bits and finish bucket by bucket: random keys overflow the
     distinct-key limit of the wave-per-bucket kernel and go through the LDS digit passes, the 3 000- and 1 800-tuple
     hubs of 40 keys through the LDS passes / the wave kernel's largest size class, the 150 000-tuple hub through the
@@ -75,7 +87,6 @@ def test_sort_reduce_on_synthetic_tuples(n, key_bits, hub):
     import numpy as np
     import torch
     from besst_amd import pipeline
-    from oracle import c_oracle as CO
     rng = np.random.default_rng(n + key_bits)
     node_bits = (key_bits - 1) // 2
     pair = rng.integers(0, 1 << (2 * node_bits), n, dtype=np.int64)
@@ -98,17 +109,10 @@ def test_sort_reduce_on_synthetic_tuples(n, key_bits, hub):
     for _ in range(2):
         gb.reduce(keys=dk, payload=dp, n_tuples_ptr=C.c_void_p(cnt.data_ptr()), capacity=n)
     torch.cuda.synchronize()
-    want = CO.edge_rows(keys, payload)
-    r = len(want['key'])
-    assert gb.read_sizes()[1] == r        # (random keys beyond 4 M tuples: the run-grouped form overflows, the call is repeated)
-    get = lambda t, m, dt: t[:m].cpu().numpy().view(dt)
-    assert np.array_equal(get(gb.row_key, r, np.uint64), want['key'])
-    assert np.array_equal(get(gb.row_n, r, np.uint32).astype(np.int64), want['n'])
-    assert np.array_equal(get(gb.row_sum, r, np.int64), want['sum_obs'])
-    assert np.array_equal(get(gb.row_sum_sq, r, np.int64), want['sum_obs_sq'])
-    assert np.array_equal(get(gb.row_first, r, np.uint32).astype(np.int64), want['first_idx'])
-    assert np.array_equal(get(gb.obs_lo, n, np.int32).astype(np.int64), want['obs_lo'])
-    assert np.array_equal(get(gb.obs_hi, n, np.int32).astype(np.int64), want['obs_hi'])
+    n_rows = gb.read_sizes()[1]           # (random keys beyond 4 M tuples: the run-grouped form overflows, the call is repeated)
+    if n > 4 << 20:
+        assert (gb.sort_flags, gb.reduce_census(n)[0]) == LARGE_SYNTHETIC_FORMS[(n, key_bits)]
+    assert_rows(gb, n_rows, keys, payload)
 
 
 def test_pass_pool_overlapped_passes_are_independent():
@@ -152,7 +156,6 @@ def test_sort_reduce_with_offset_scaffold_ids(n):
     import numpy as np
     import torch
     from besst_amd import pipeline
-    from oracle import c_oracle as CO
     rng = np.random.default_rng(n)
     node_bits, lo_id, hi_id = 21, 600_001, 760_000
     rows = max(1000, n // 12)
@@ -179,23 +182,21 @@ def test_sort_reduce_with_offset_scaffold_ids(n):
     cnt = torch.tensor([n], dtype=torch.int32, device=dev)
     gb.reduce(keys=dk, payload=dp, n_tuples_ptr=C.c_void_p(cnt.data_ptr()), capacity=n)
     torch.cuda.synchronize()
-    want = CO.edge_rows(keys, payload)
-    r = len(want['key'])
-    assert gb.read_sizes()[1] == r
-    get = lambda t, m, dt: t[:m].cpu().numpy().view(dt)
-    assert np.array_equal(get(gb.row_key, r, np.uint64), want['key'])
-    assert np.array_equal(get(gb.row_n, r, np.uint32).astype(np.int64), want['n'])
-    assert np.array_equal(get(gb.row_sum, r, np.int64), want['sum_obs'])
-    assert np.array_equal(get(gb.row_first, r, np.uint32).astype(np.int64), want['first_idx'])
-    assert np.array_equal(get(gb.obs_lo, n, np.int32).astype(np.int64), want['obs_lo'])
+    n_rows = gb.read_sizes()[1]
+    if n > 4 << 20:
+        assert (gb.key_bits, gb.sort_flags, gb.reduce_census(n)[0]) == {6_000_000: (41, 1, 2), 24_000_000: (41, 1, 3)}[n]
+    assert_rows(gb, n_rows, keys, payload)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('n', [0, 1, 100, 70_000])
-def test_large_capacity_with_few_tuples(n):
-    """The sort path is chosen by the CAPACITY of the tuple buffers (a resident builder is sized for the largest pass):
-    the chained-scan passes + wave-per-bucket kernels with a stream of 0, 1 and a few tuples (every bucket but a handful
-    empty, n_rows from the last workgroup of the row mover), and 70 000 tuples that still fit one scatter tile each."""
+@pytest.mark.parametrize('n,sort_flags', [(n, f) for n in (0, 1, 100, 70_000) for f in (0, 1)],
+                         ids=['%d%s' % (n, '-no_runs' if f else '') for n in (0, 1, 100, 70_000) for f in (0, 1)])
+def test_large_capacity_with_few_tuples(n, sort_flags):
+    """The sort path is chosen by the CAPACITY of the tuple buffers (a resident builder is sized for the largest pass): 5 M
+    slots with a stream of 0, 1 and a few tuples, and 70 000 tuples that still fit one scatter tile each.  Without a flag
+    that is the run-grouped form (a handful of chunks, the rest of the grid empty); with BESST_REDUCE_NO_RUNS the
+    chained-scan passes + wave-per-bucket kernels (every bucket but a handful empty, n_rows from the last workgroup of
+    the row mover).  The form is asserted (besst_dev_reduce_census)."""
     import ctypes as C
     import numpy as np
     import torch
@@ -214,6 +215,8 @@ def test_large_capacity_with_few_tuples(n):
     lib = dict(read_len=100.0, ins_size_threshold=800.0, min_mapq=11, orientation='fr', detect_duplicate=True,
                extend_paths=True, no_score=False)
     gb = pipeline.DeviceGraphBuilder(dev, 4, node_bits, lib, cap, cap)
+    assert sort_flags in (0, pipeline.REDUCE_NO_RUNS)
+    gb.sort_flags = sort_flags
     dk = torch.zeros(cap, dtype=torch.int64, device=dev)
     dp = torch.zeros(cap, dtype=torch.int64, device=dev)
     dk[:n] = torch.from_numpy(keys.view(np.int64)).to(dev)
@@ -224,16 +227,20 @@ def test_large_capacity_with_few_tuples(n):
     torch.cuda.synchronize()
     want = CO.edge_rows(keys, payload)
     r = len(want['key'])
-    assert gb.read_sizes()[1] == r
+    n_rows = gb.read_sizes()[1]
+    assert gb.sort_flags == sort_flags and gb.reduce_census(cap)[0] == (2 if sort_flags else 1)
+    assert_rows(gb, n_rows, keys, payload)
     get = lambda t, m, dt: t[:m].cpu().numpy().view(dt)
-    assert np.array_equal(get(gb.row_key, r, np.uint64), want['key'])
-    assert np.array_equal(get(gb.row_n, r, np.uint32).astype(np.int64), want['n'])
-    assert np.array_equal(get(gb.row_sum, r, np.int64), want['sum_obs'])
-    assert np.array_equal(get(gb.row_sum_sq, r, np.int64), want['sum_obs_sq'])
-    assert np.array_equal(get(gb.row_first, r, np.uint32).astype(np.int64), want['first_idx'])
     assert np.array_equal(get(gb.row_mask, r, np.uint32).astype(np.int64), np.ones(r, np.int64))
-    assert np.array_equal(get(gb.obs_lo, n, np.int32).astype(np.int64), want['obs_lo'])
-    assert np.array_equal(get(gb.obs_hi, n, np.int32).astype(np.int64), want['obs_hi'])
+
+
+# (key_bits, links per edge) -> top-16-bit buckets that are empty / finished by the wave kernel / by its digit passes, as
+# besst_dev_reduce_census reported them for the seeded streams below (tests/sort_design.predict_chained gives the same);
+# no bucket is large enough for the workgroup kernel
+BUCKET_FORM_CENSUS = {(25, 1): [0, 52899, 12637], (25, 40): [12713, 52823, 0], (26, 1): [32768, 5, 32763],
+                      (26, 40): [33991, 31545, 0], (31, 1): [0, 45110, 20426], (31, 40): [12633, 52903, 0],
+                      (33, 1): [0, 44870, 20666], (33, 40): [12696, 52840, 0], (40, 1): [32768, 1, 32767],
+                      (40, 40): [33970, 31566, 0], (41, 1): [0, 44923, 20613], (41, 40): [12534, 53002, 0]}
 
 
 @pytest.mark.gpu
@@ -241,8 +248,14 @@ def test_large_capacity_with_few_tuples(n):
 @pytest.mark.parametrize('key_bits', [25, 26, 31, 33, 40, 41])
 def test_bucket_form_over_the_key_widths(key_bits, links_per_edge):
     """The two-pass + buckets form of the large-stream sort serves packed keys of 25 to 41 significant bits (with 4.3 M
-    tuples): 9 to 25 key bits are left to the buckets.  One link per edge sends every bucket through the digit-pass
-    kernels (one or more 7-bit passes), forty links per edge through the wave kernel's smallest-key peel."""
+    tuples): 9 to 25 key bits are left to the buckets.  Forty links per edge send every bucket through the wave kernel's
+    smallest-key peel.  One link per edge - the edges are drawn with replacement, so a bucket's ~65 (even widths: ~130,
+    the top key bit is never set) tuples hold ~41 (~82) distinct keys, on either side of the wave kernel's 48 - sends a
+    fifth to all of the non-empty buckets through the digit-pass kernel (one or more 7-bit passes), the others through
+    the wave kernel.  The keys are random, so the call is first made in the run-grouped form, overflows its run buffers,
+    and read_sizes() repeats it with BESST_REDUCE_NO_RUNS: the flag, the form and the number of buckets each bucket
+    kernel finished (BUCKET_FORM_CENSUS) are asserted; the borders themselves are designed in
+    tests/test_gpu_sort_classes.py."""
     import ctypes as C
     import numpy as np
     import torch
@@ -272,12 +285,9 @@ def test_bucket_form_over_the_key_widths(key_bits, links_per_edge):
     torch.cuda.synchronize()
     want = CO.edge_rows(keys, payload)
     r = len(want['key'])
-    assert gb.read_sizes()[1] == r
-    get = lambda t, m, dt: t[:m].cpu().numpy().view(dt)
-    assert np.array_equal(get(gb.row_key, r, np.uint64), want['key'])
-    assert np.array_equal(get(gb.row_n, r, np.uint32).astype(np.int64), want['n'])
-    assert np.array_equal(get(gb.row_sum, r, np.int64), want['sum_obs'])
-    assert np.array_equal(get(gb.row_sum_sq, r, np.int64), want['sum_obs_sq'])
-    assert np.array_equal(get(gb.row_first, r, np.uint32).astype(np.int64), want['first_idx'])
-    assert np.array_equal(get(gb.obs_lo, n, np.int32).astype(np.int64), want['obs_lo'])
-    assert np.array_equal(get(gb.obs_hi, n, np.int32).astype(np.int64), want['obs_hi'])
+    n_rows = gb.read_sizes()[1]
+    assert n_rows == r
+    census = gb.reduce_census(n)
+    assert gb.sort_flags == pipeline.REDUCE_NO_RUNS and census[0] == 2, 'the stream was meant for the chained scan + buckets'
+    assert census[1:] == BUCKET_FORM_CENSUS[(key_bits, links_per_edge)] + [0, 0, 0, 0], census
+    assert_rows(gb, n_rows, keys, payload)

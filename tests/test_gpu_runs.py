@@ -1,5 +1,5 @@
 """The run-grouped form of stage 2 (csrc/runs.hip) on tuple streams beyond 4 M tuples: runs of equal keys inside chunks
-of 1024 consecutive tuples are what gets sorted.  Checked against the numpy aggregation of the same stream
+of kRunChunk (512) consecutive tuples are what gets sorted.  Checked against the numpy aggregation of the same stream
 (oracle.c_oracle.edge_rows: stable sort by key, exact sums) - CreateGraph.py:842-862."""
 import ctypes as C
 import os
@@ -45,7 +45,9 @@ def clustered_stream(n, node_bits, noise, seed, hub=0, links=40, spread=24):
     return keys, lo | (hi << np.uint64(32))
 
 
-def run_reduce(keys, payload, node_bits, cap=None, first_map=None, flags=0):
+def run_reduce(keys, payload, node_bits, cap=None, first_map=None, flags=0, key_bits=None, key_base=None):
+    """Stage 2 alone on a stream in `cap` slots (default: as many as tuples), twice on one builder.  key_bits / key_base:
+    the key range the sort is told (default: 2 * node_bits + 1 bits from 0)."""
     import torch
     from besst_amd import pipeline
     n = len(keys)
@@ -53,6 +55,10 @@ def run_reduce(keys, payload, node_bits, cap=None, first_map=None, flags=0):
     dev = torch.device('cuda', 0)
     gb = pipeline.DeviceGraphBuilder(dev, 4, node_bits, LIB, 1, cap)
     gb.sort_flags = flags
+    if key_bits is not None:
+        gb.key_bits = key_bits
+    if key_base is not None:
+        gb.key_base = key_base
     dk = torch.zeros(cap, dtype=torch.int64, device=dev)
     dp = torch.zeros(cap, dtype=torch.int64, device=dev)
     dk[:n] = torch.from_numpy(keys.view(np.int64)).to(dev)
@@ -260,7 +266,7 @@ def test_partitions_on_several_streams_do_not_wait_for_each_other():
 def test_sparse_segments_chunks_spanning_many_blocks(monkeypatch):
     """The fused record loop hands its block segments over; a capacity beyond 4 M tuples picks the run-grouped form
     whatever the stream holds.  Long contigs and short inserts leave a dozen tuples per 16 384-record block, so a
-    chunk of 1024 tuples spans more than the 64 blocks a wave keeps in its lanes and looks its blocks up in memory."""
+    chunk of 512 tuples spans more than the 64 blocks a wave keeps in its lanes and looks its blocks up in memory."""
     import torch
     from besst_amd import pipeline, synth, workload
     from oracle import c_oracle as CO
