@@ -7,14 +7,9 @@
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
-#include <thread>
-#include <chrono>
-#include <mutex>
-#include <type_traits>
 #include <vector>
 
-#include "common.h"
+#include "context.h"
 
 namespace besst {
 
@@ -53,31 +48,6 @@ ProfScope::~ProfScope() {
 
 namespace {
 
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;   // elements
-    int ensure(size_t n) {
-        if (n <= cap) return BESST_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = n + n / 8 + 64;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T));
-        if (e != hipSuccess) {
-            set_error("hipMalloc(%zu bytes) failed: %s", want * sizeof(T), hipGetErrorString(e));
-            return BESST_ERR_NOMEM;
-        }
-        cap = want;
-        return BESST_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int bits_for(uint64_t v) {
@@ -92,163 +62,7 @@ int bits_for(uint64_t v) {
 
 using namespace besst;
 
-// ---- pinned staging buffers are kept -------------------------------------------------------------------------------
-// Pinning and unpinning host memory costs ~90 ms per GB on the bench host - 47 of the 220 ms an ingest of a 40 M-record
-// file took, most of it the release at the end of the call.  The staging buffers of the two ingest forms therefore come
-// from a process-wide pool and go back to it: a later call (the next library's file, the other form, the next context)
-// finds them pinned.  The pool holds at most kPinnedKeep bytes (what comes back beyond that is freed), is never freed at
-// exit (the runtime may be gone by then), and besst_release_cached_memory() empties it.
 namespace {
-// Work nobody waits for (freeing an ingest's device scratch): threads that are joined when the next one starts, when a
-// context is destroyed and by besst_release_cached_memory() - never left running behind the library's last call.
-struct Background {
-    std::mutex mu;
-    std::vector<std::thread> threads;
-    ~Background() {                                          // (process exit with a context never destroyed: let them go)
-        for (std::thread& t : threads)
-            if (t.joinable()) t.detach();
-    }
-    void join_all() {
-        std::vector<std::thread> mine;
-        {
-            std::lock_guard<std::mutex> g(mu);
-            mine.swap(threads);
-        }
-        for (std::thread& t : mine)
-            if (t.joinable()) t.join();
-    }
-    template <class F>
-    void run(F f) {
-        join_all();
-        std::lock_guard<std::mutex> g(mu);
-        threads.emplace_back(std::move(f));
-    }
-};
-Background g_background;
-
-// What every device ingest needs whatever the file: four streams (4 ms each to create: 17 of a call's 18 ms of set-up), twelve
-// events and three small buffers.  One set per device stays with the process; a call takes it (a second call on the same
-// device at the same time makes its own and destroys it), besst_release_cached_memory() does not touch it (a few KB).
-struct IngestKit {
-    std::mutex mu;
-    bool busy = false;
-    hipStream_t work[3] = {nullptr, nullptr, nullptr}, copy = nullptr;
-    hipEvent_t ev[3][4] = {};
-    char* heads = nullptr;
-    size_t heads_bytes = 0;
-    uint32_t* d_flags = nullptr;
-    uint32_t* summ_host = nullptr;
-};
-IngestKit g_ingest_kit[16];
-constexpr size_t kPinnedKeep = (size_t)1 << 30;
-struct PinnedPool {
-    struct Entry { void* p; size_t bytes; bool busy; };
-    std::mutex mu;
-    std::vector<Entry> all;
-    void* acquire(size_t bytes) {
-        {
-            std::lock_guard<std::mutex> g(mu);
-            Entry* best = nullptr;
-            for (Entry& e : all)
-                if (!e.busy && e.bytes >= bytes && e.bytes <= bytes + bytes / 2 + ((size_t)1 << 20) && (!best || e.bytes < best->bytes)) best = &e;
-            if (best) { best->busy = true; return best->p; }
-        }
-        void* p = nullptr;
-        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
-            trim(0);                                          // (what is cached may be what is missing)
-            if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
-        }
-        std::lock_guard<std::mutex> g(mu);
-        all.push_back(Entry{p, bytes, true});
-        return p;
-    }
-    void give_back(void* p) {
-        if (!p) return;
-        {
-            std::lock_guard<std::mutex> g(mu);
-            for (Entry& e : all)
-                if (e.p == p) e.busy = false;
-        }
-        trim(kPinnedKeep);
-    }
-    // free idle buffers, largest first, until at most `keep` idle bytes are left
-    void trim(size_t keep) {
-        for (;;) {
-            void* victim = nullptr;
-            {
-                std::lock_guard<std::mutex> g(mu);
-                size_t idle = 0;
-                size_t at = all.size();
-                for (size_t i = 0; i < all.size(); ++i)
-                    if (!all[i].busy) {
-                        idle += all[i].bytes;
-                        if (at == all.size() || all[i].bytes > all[at].bytes) at = i;
-                    }
-                if (idle <= keep || at == all.size()) return;
-                victim = all[at].p;
-                all.erase(all.begin() + (long)at);
-            }
-            (void)hipHostFree(victim);
-        }
-    }
-};
-PinnedPool g_pinned;
-}  // namespace
-
-struct besst_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    // contig table
-    int64_t n_contigs = 0;
-    int32_t node_bits = 1;
-    uint64_t key_base = 0;
-    int32_t key_bits = 3;
-    DevBuf<ContigRow> table;
-    DevBuf<int64_t> aligned;
-    // library
-    bool have_lib = false;
-    besst_lib_params lib{};
-    // resident records
-    int64_t n_records = 0;
-    DevBuf<int32_t> tid, mtid, pos, mpos, tlen;
-    DevBuf<uint16_t> flag, qlen;
-    DevBuf<uint8_t> mapq;
-    DevBuf<uint8_t> mate_bits;       // one bit per record: tid != mtid (ClassifyArgs::mate_bits), valid for the first bits_upto records
-    int64_t bits_upto = 0;
-    // tuple stream + edge table
-    DevBuf<uint64_t> keys, payload, row_key;
-    DevBuf<uint32_t> row_mask, row_n, row_first, row_offset;
-    DevBuf<int64_t> row_sum, row_sum_sq;
-    DevBuf<int32_t> obs_lo, obs_hi;
-    DevBuf<int32_t> obs_sum;         // besst_ctx_fetch_observation_sums: obs_lo + obs_hi, made and copied on side_stream
-    hipStream_t side_stream = nullptr;
-    DevBuf<char> ws;
-    DevBuf<char> small;      // counters + carry + n_out + n_rows
-    bool built = false;
-    int64_t n_rows = 0, n_tuples = 0;
-    // misc scratch for metrics / scoring
-    DevBuf<uint8_t> top_mask;
-    DevBuf<int32_t> sample_a, sample_b;
-    DevBuf<char> aux;
-    // prefix tables of the log-normal pmf (besst_ctx_score_edges_lognormal), kept while (mu, sigma, x_max) stay the same
-    DevBuf<double> ln_tables;
-    double ln_mu = 0.0, ln_sigma = 0.0;
-    int64_t ln_x_max = 0;
-};
-
-namespace {
-
-struct SmallBlock {
-    besst_counters counters;
-    int32_t carry[2];
-    uint32_t n_out;
-    uint32_t n_rows;
-};
-
-int use_device(besst_ctx* c) {
-    BESST_HIP_TRY(hipSetDevice(c->device));
-    return BESST_OK;
-}
 
 template <typename T>
 int grow_copy(besst_ctx* c, DevBuf<T>& buf, int64_t have, const T* src, int64_t n) {
@@ -272,11 +86,6 @@ extern "C" {
 int besst_abi_version(void) { return BESST_ABI_VERSION; }
 
 const char* besst_last_error(void) { return g_error; }
-
-void besst_release_cached_memory(void) {
-    g_background.join_all();
-    g_pinned.trim(0);
-}
 
 void besst_prof_enable(uint32_t slot_mask) {
     g_prof_mask = slot_mask;
@@ -358,7 +167,7 @@ besst_ctx* besst_ctx_create(int device) {
 
 void besst_ctx_destroy(besst_ctx* c) {
     if (!c) return;
-    g_background.join_all();
+    ingest_join_background();
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     c->table.release(); c->aligned.release();
@@ -518,902 +327,6 @@ int besst_ctx_fetch_records(besst_ctx* c, int64_t first, int64_t n, int32_t* tid
     BESST_HIP_TRY(down(mapq, c->mapq.p + first, m));
     BESST_HIP_TRY(down(qlen, c->qlen.p + first, m * 2));
     BESST_HIP_TRY(hipStreamSynchronize(c->stream));
-    return BESST_OK;
-}
-
-// Reserve room for `total` records in every column (one reallocation + device copy instead of a chain of them).
-static int reserve_records(besst_ctx* c, int64_t total) {
-    const int64_t have = c->n_records;
-    auto grow = [&](auto& buf) -> int {
-        using T = typename std::remove_reference<decltype(*buf.p)>::type;
-        if ((size_t)total <= buf.cap) return BESST_OK;
-        DevBuf<T> bigger;
-        int rc = bigger.ensure((size_t)total);
-        if (rc) return rc;
-        if (have) BESST_HIP_TRY(hipMemcpyAsync(bigger.p, buf.p, (size_t)have * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-        BESST_HIP_TRY(hipStreamSynchronize(c->stream));
-        buf.release();
-        buf = bigger;
-        return BESST_OK;
-    };
-    int rc;
-    if ((rc = grow(c->tid)) || (rc = grow(c->mtid)) || (rc = grow(c->pos)) || (rc = grow(c->mpos)) || (rc = grow(c->tlen)) ||
-        (rc = grow(c->flag)) || (rc = grow(c->mapq)) || (rc = grow(c->qlen)))
-        return rc;
-    return BESST_OK;
-}
-
-// BAM file -> resident records, streamed: chunks of the file are inflated and decoded by the reader's host threads into
-// one of two sets of PINNED staging columns while the previous chunk's eight asynchronous copies are still on their way
-// to HBM - decode and upload overlap, no pageable copy, no host-side concatenation of the whole stream.
-int besst_ctx_push_bam(besst_ctx* c, besst_bam* bam, int64_t chunk_records, int64_t head_records, int32_t* head_rlen,
-                       int32_t* head_alen, uint16_t* head_qlen, besst_ingest_stats* stats) {
-    BESST_REQUIRE(c && bam, "push_bam: null context or reader");
-    BESST_REQUIRE(head_records >= 0 && (head_records == 0 || (head_rlen && head_alen && head_qlen)), "push_bam: head buffers missing");
-    if (chunk_records <= 0) chunk_records = (int64_t)4 << 20;
-    if (chunk_records < 1024) chunk_records = 1024;
-    int rc = use_device(c);
-    if (rc) return rc;
-    const auto t_start = std::chrono::steady_clock::now();
-    struct Slot {
-        int32_t *tid = nullptr, *mtid = nullptr, *pos = nullptr, *mpos = nullptr, *tlen = nullptr;
-        uint16_t *flag = nullptr, *qlen = nullptr;
-        uint8_t* mapq = nullptr;
-        hipEvent_t done = nullptr;
-        bool busy = false;
-    } slot[2];
-    std::vector<int32_t> rlen((size_t)chunk_records), alen((size_t)chunk_records);
-    auto release = [&]() {
-        for (Slot& sl : slot) {
-            void* ptrs[8] = {sl.tid, sl.mtid, sl.pos, sl.mpos, sl.tlen, sl.flag, sl.qlen, sl.mapq};
-            for (void* q : ptrs) g_pinned.give_back(q);
-            if (sl.done) (void)hipEventDestroy(sl.done);
-            sl = Slot();
-        }
-    };
-    auto pinned = [&](void** out, size_t bytes) { return (*out = g_pinned.acquire(bytes)) != nullptr; };
-    bool ok = true;
-    for (Slot& sl : slot) {
-        const size_t m = (size_t)chunk_records;
-        ok = ok && pinned((void**)&sl.tid, m * 4) && pinned((void**)&sl.mtid, m * 4) && pinned((void**)&sl.pos, m * 4) &&
-             pinned((void**)&sl.mpos, m * 4) && pinned((void**)&sl.tlen, m * 4) && pinned((void**)&sl.flag, m * 2) &&
-             pinned((void**)&sl.qlen, m * 2) && pinned((void**)&sl.mapq, m) && hipEventCreate(&sl.done) == hipSuccess;
-    }
-    if (!ok) {
-        release();
-        set_error("push_bam: cannot allocate pinned staging buffers (2 x %lld records)", (long long)chunk_records);
-        return BESST_ERR_NOMEM;
-    }
-    double decode_s = 0.0, wait_s = 0.0;
-    int64_t pushed = 0, chunks = 0, bytes = 0;
-    const int64_t file_bytes = bam_file_bytes(bam);
-    rc = BESST_OK;
-    for (int k = 0;; k ^= 1) {
-        Slot& sl = slot[k];
-        if (sl.busy) {                                       // the copies that last used this slot
-            const auto t0 = std::chrono::steady_clock::now();
-            if (hipEventSynchronize(sl.done) != hipSuccess) { set_error("push_bam: a host-to-device copy failed"); rc = BESST_ERR_HIP; break; }
-            wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            sl.busy = false;
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        const int64_t got = besst_bam_read_records(bam, chunk_records, sl.tid, sl.mtid, sl.pos, sl.mpos, sl.tlen, sl.flag, sl.mapq,
-                                                   sl.qlen, rlen.data(), alen.data());
-        decode_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (got < 0) { rc = (int)-got; break; }              // (the reader has set the error text)
-        if (got == 0) break;
-        for (int64_t i = 0; i < got && pushed + i < head_records; ++i) {
-            head_rlen[pushed + i] = rlen[(size_t)i];
-            head_alen[pushed + i] = alen[(size_t)i];
-            head_qlen[pushed + i] = sl.qlen[i];
-        }
-        const int64_t have = c->n_records + pushed;
-        if (have + got >= ((int64_t)1 << 32)) { set_error("more than 2^32-1 records in one context"); rc = BESST_ERR_ARG; break; }
-        if ((size_t)(have + got) > c->tid.cap) {
-            // room for the whole file at the rate of the bytes read so far (+ 6 %), at least for this chunk
-            const int64_t at = bam_file_position(bam);
-            int64_t want = have + got;
-            if (file_bytes > 0 && at > 0 && at < file_bytes)
-                want = c->n_records + (int64_t)((double)(pushed + got) * ((double)file_bytes / (double)at) * 1.06) + 4096;
-            if (want < have + got) want = have + got;
-            if (want >= ((int64_t)1 << 32)) want = ((int64_t)1 << 32) - 1;
-            const int64_t keep = c->n_records;
-            c->n_records = have;                             // what reserve_records has to carry over
-            rc = reserve_records(c, want);
-            c->n_records = keep;
-            if (rc) break;
-        }
-        const size_t m = (size_t)got;
-        hipError_t e = hipSuccess;
-        auto up = [&](void* dst, const void* src, size_t nbytes) {
-            if (e == hipSuccess) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyHostToDevice, c->stream);
-            bytes += (int64_t)nbytes;
-        };
-        up(c->tid.p + have, sl.tid, m * 4); up(c->mtid.p + have, sl.mtid, m * 4); up(c->pos.p + have, sl.pos, m * 4);
-        up(c->mpos.p + have, sl.mpos, m * 4); up(c->tlen.p + have, sl.tlen, m * 4); up(c->flag.p + have, sl.flag, m * 2);
-        up(c->mapq.p + have, sl.mapq, m); up(c->qlen.p + have, sl.qlen, m * 2);
-        if (e == hipSuccess) e = hipEventRecord(sl.done, c->stream);
-        if (e != hipSuccess) { set_error("push_bam: %s", hipGetErrorString(e)); rc = BESST_ERR_HIP; break; }
-        sl.busy = true;
-        pushed += got;
-        ++chunks;
-    }
-    const auto tw = std::chrono::steady_clock::now();
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
-    release();
-    if (rc == BESST_OK && es != hipSuccess) { set_error("push_bam: %s", hipGetErrorString(es)); rc = BESST_ERR_HIP; }
-    if (rc) return rc;
-    c->n_records += pushed;
-    c->built = false;
-    if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        stats->records = pushed;
-        stats->chunks = chunks;
-        stats->bytes_h2d = bytes;
-        stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-        stats->decode_seconds = decode_s;
-        stats->copy_wait_seconds = wait_s;
-    }
-    return BESST_OK;
-}
-
-// ---- BAM ingest on the GPU (bgzf_gpu.hip) ----------------------------------------------------------------------------
-namespace {
-
-// The BGZF blocks of [*fpos, ...) that fit one chunk: descriptors with offsets relative to the chunk's first byte,
-// inflated places 256-byte aligned.  Stops at max_blocks, at comp_cap compressed bytes, or at the end of the file.
-// false: not a BGZF block where one should be.
-// dst0 / back_to_back: where the first block's bytes go and whether the blocks follow each other without padding (the
-// ingest: a record may run on into the next block) or at 256-byte boundaries (the inflate test hook)
-bool scan_bgzf_chunk(const uint8_t* map, size_t map_len, size_t* fpos, size_t max_blocks, size_t comp_cap, BgzfBlock* out,
-                     uint32_t* n_out, size_t* comp_bytes, size_t* inflated_bytes, bool more_follows = false, size_t dst0 = 0,
-                     bool back_to_back = false) {
-    auto le16 = [](const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); };
-    auto le32 = [](const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); };
-    const size_t begin = *fpos;
-    size_t at = begin, dst = dst0;
-    uint32_t n = 0;
-    while (n < max_blocks && at < map_len) {
-        const uint8_t* hdr = map + at;
-        if (map_len - at < 18) {                             // `map` is a window of the file: the block continues behind it
-            if (more_follows) break;
-            return false;
-        }
-        if (hdr[0] != 31 || hdr[1] != 139 || hdr[2] != 8 || !(hdr[3] & 4)) return false;
-        const uint32_t xlen = le16(hdr + 10);
-        if (xlen < 6 || hdr[12] != 'B' || hdr[13] != 'C' || le16(hdr + 14) != 2) return false;
-        const size_t bsize = (size_t)le16(hdr + 16) + 1;
-        if (bsize < 18) return false;
-        if (map_len - at < bsize) {
-            if (more_follows) break;
-            return false;
-        }
-        const size_t rest = bsize - 18, extra_left = xlen - 6;
-        if (rest < extra_left + 8) return false;
-        if (at + bsize - begin > comp_cap) {
-            if (n == 0) return false;                        // (a block is at most 64 KiB: the cap is far larger)
-            break;
-        }
-        const uint32_t isize = le32(hdr + bsize - 4);
-        if (isize > 65536u) return false;
-        BgzfBlock& b = out[n++];
-        b.src_off = (uint32_t)(at + 18 + extra_left - begin);
-        b.src_len = (uint32_t)(rest - extra_left - 8);
-        b.dst_off_lo = (uint32_t)dst;
-        b.dst_off_hi = (uint32_t)((uint64_t)dst >> 32);
-        b.dst_len = isize;
-        b.crc = le32(hdr + bsize - 8);
-        dst += back_to_back ? (size_t)isize : align_up((size_t)isize, 256);
-        at += bsize;
-    }
-    *fpos = at;
-    *n_out = n;
-    *comp_bytes = at - begin;
-    *inflated_bytes = dst - dst0;
-    return true;
-}
-
-// First BGZF block boundary at or behind `from`: the gzip magic with the BC subfield, a plausible BSIZE, and two further
-// blocks (or the end of the file) chained behind it - payload bytes that happen to spell a header do not survive that.
-size_t find_bgzf_boundary(const uint8_t* map, size_t map_len, size_t from) {
-    auto le16 = [](const uint8_t* p) { return (size_t)p[0] | ((size_t)p[1] << 8); };
-    auto block_at = [&](size_t at, size_t* bsize) {
-        if (map_len - at < 28) return false;
-        const uint8_t* h = map + at;
-        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4) || le16(h + 10) < 6 || h[12] != 'B' || h[13] != 'C' || le16(h + 14) != 2)
-            return false;
-        *bsize = le16(h + 16) + 1;
-        return *bsize >= 28 && *bsize <= map_len - at;
-    };
-    for (size_t at = from; at + 28 <= map_len; ++at) {
-        size_t b0 = 0, b1 = 0, b2 = 0;
-        if (!block_at(at, &b0)) continue;
-        const size_t n1 = at + b0;
-        if (n1 == map_len) return at;
-        if (!block_at(n1, &b1)) continue;
-        const size_t n2 = n1 + b1;
-        if (n2 == map_len || block_at(n2, &b2)) return at;
-    }
-    return map_len;
-}
-
-}  // namespace
-
-// BAM file -> resident records with the inflate and the record decode on the GPU: the file's COMPRESSED bytes are read into
-// pinned memory by the reader's threads and uploaded chunk by chunk; per chunk one wave per BGZF block inflates, one lane per
-// block walks its records, a scan places them and a thread per record fills the columns.  Three slots, each with its own
-// staging, scratch and stream: chunk j + 1 is INFLATING and chunk j + 2 read, uploaded and queued behind it while the host
-// waits for chunk j's record count (the columns may have to grow before its decode) - the tail of one chunk's waves and the
-// head of the next share the chip.  Any block layout: a chunk's blocks are inflated back to back behind a slot that receives the record the chunk before
-// left unfinished, and the record starts are guessed per block and verified from block to block (bgzf_gpu.hip).  A block
-// the device cannot inflate returns BESST_ERR_UNSUPPORTED with context and reader untouched, and the caller takes
-// besst_ctx_push_bam.
-int besst_ctx_push_bam_device(besst_ctx* c, besst_bam* bam, int64_t chunk_blocks, int64_t head_records, int32_t* head_rlen,
-                              int32_t* head_alen, uint16_t* head_qlen, besst_ingest_stats* stats) {
-    return besst_ctx_push_bam_device_part(c, bam, 0, 1, chunk_blocks, head_records, head_rlen, head_alen, head_qlen, stats);
-}
-
-// The same for ONE PART of the file's records (multi-GPU ingest: rank r of W takes part r of W and holds the r-th slice of
-// the stream, which is what phase 1 of the sharded build works on): the file is cut at the BGZF block boundaries nearest
-// to part / parts of its bytes - in htslib's layout every block begins with a record, so every boundary is a valid place
-// to start, and every rank finds the same boundaries on its own.
-namespace {
-// first_skip / boundary: the slice form (besst_ctx_push_bam_device_slice; boundary == nullptr: the part form, which takes
-// htslib's layout only and begins every part with its first block's first byte).
-int push_bam_device_impl(besst_ctx* c, besst_bam* bam, int32_t part, int32_t parts, int64_t chunk_blocks, int64_t head_records,
-                         int32_t* head_rlen, int32_t* head_alen, uint16_t* head_qlen, besst_ingest_stats* stats,
-                         int64_t first_skip, int64_t* boundary) {
-    BESST_REQUIRE(c && bam, "push_bam_device: null context or reader");
-    BESST_REQUIRE(parts >= 1 && part >= 0 && part < parts, "push_bam_device: part must be in [0, parts)");
-    BESST_REQUIRE(head_records >= 0 && (head_records == 0 || (head_rlen && head_alen && head_qlen)),
-                  "push_bam_device: head buffers missing");
-    if (chunk_blocks <= 0) chunk_blocks = 5120;              // (one full chip of the inflate kernel's waves: 1024 SIMDs x 5; twice that reads 10 % slower)
-    if (chunk_blocks < 64) chunk_blocks = 64;
-    if (chunk_blocks > 65536) chunk_blocks = 65536;
-    int rc = use_device(c);
-    if (rc) return rc;
-    const auto t_start = std::chrono::steady_clock::now();
-    int64_t f0 = 0;
-    uint32_t u0 = 0;
-    if (!bam_record_position(bam, &f0, &u0)) {
-        set_error("push_bam_device: the reader is inside a record that straddles two batches");
-        return BESST_ERR_UNSUPPORTED;
-    }
-    size_t map_len = (size_t)bam_file_bytes(bam);        // (from here on: the end of this call's part of the file)
-    const size_t whole_file = map_len;
-    const bool slice = boundary != nullptr;
-    if (parts > 1) {
-        const uint8_t* map = bam_file_map(bam);
-        const size_t file_len = map_len;
-        auto cut = [&](int32_t k) -> size_t {
-            if (k <= 0) return (size_t)f0;
-            if (k >= parts) return file_len;
-            const size_t at = find_bgzf_boundary(map, file_len, (size_t)((double)file_len * (double)k / (double)parts));
-            return at < (size_t)f0 ? (size_t)f0 : at;
-        };
-        const size_t begin = cut(part);
-        map_len = cut(part + 1);
-        if (begin != (size_t)f0) u0 = 0;
-        f0 = (int64_t)begin;
-        if (map_len < begin) map_len = begin;
-    }
-    size_t nb = (size_t)chunk_blocks;
-    // a chunk: nb blocks or comp_cap compressed bytes, whichever comes first.  The staging slots are pinned (~70 us per
-    // MB to allocate and release), so they are sized from the file's first blocks - ~5 KB each in a file of constant
-    // qualities, ~18 KB in a sequencer's - with a third in hand; denser blocks further on just make a chunk hold fewer.
-    // A file (or part) of fewer blocks than a chunk gets slots for what it holds: every slot carries 64 KiB of inflated
-    // scratch per block, 0.5 GB at the default chunk, whatever the file's size.
-    size_t comp_cap = (size_t)160 << 20;
-    double first_per_block = 0.0;                            // compressed bytes per block over the file's first blocks
-    {
-        const uint8_t* map = bam_file_map(bam);
-        size_t at = (size_t)f0, seen = 0;
-        while (seen < 256 && at + 18 <= map_len && map[at] == 31 && map[at + 1] == 139) {
-            at += ((size_t)map[at + 16] | ((size_t)map[at + 17] << 8)) + 1;
-            ++seen;
-        }
-        if (seen >= 1 && at <= map_len + 65536) {
-            const double per_block = (double)(at - (size_t)f0) / (double)seen;
-            if (seen >= 16) first_per_block = per_block;
-            const size_t blocks = at >= map_len ? seen : (size_t)((double)(map_len - (size_t)f0) / per_block * 1.25) + 64;
-            if (blocks < nb) nb = blocks < 64 ? 64 : blocks;
-        }
-        if (seen >= 16 && at <= map_len) {
-            const size_t guess = align_up((size_t)((double)(at - (size_t)f0) / (double)seen * (double)nb * 1.35) + ((size_t)4 << 20), 4096);
-            if (guess < comp_cap) comp_cap = guess;
-        }
-    }
-    if (comp_cap > map_len - (size_t)f0 + 65536) comp_cap = align_up(map_len - (size_t)f0 + 65536, 4096);
-    if (comp_cap < ((size_t)1 << 20)) comp_cap = (size_t)1 << 20;
-    // descriptor 0 of every chunk is the slot for the tail of the chunk before (a record that its bytes did not finish)
-    const size_t nbw = nb + 1;
-    constexpr size_t kTailRoom = (size_t)4 << 20;            // bytes a chunk may carry into the next one (one record)
-    const size_t desc_bytes = align_up(nbw * sizeof(BgzfBlock), 4096);
-    const size_t slot_bytes = desc_bytes + comp_cap + 4096;      // (the bit reader's windows run up to 512 bytes past a payload)
-    struct Chunk { uint32_t n_blocks = 0, first_off = 0; size_t comp = 0, inflated = 0, file_end = 0; };
-    constexpr int kSlots = 3;        // chunk j's starts being verified, j + 1 inflating, j + 2 on its way to the device
-    struct Slot {
-        char* pin = nullptr;         // pinned: descriptors, then the chunk's bytes as they lie in the file
-        char* dev = nullptr;         // the same on the device
-        uint8_t* inflated = nullptr;
-        uint32_t* symbols = nullptr; // the inflate kernel's symbol buffer: four bytes per byte of `inflated` (touched: per symbol)
-        uint16_t* offs = nullptr;
-        uint32_t* words = nullptr;   // status | count | exits | rec_base | guess | tail_at (nbw each), then 8 summary words
-        hipStream_t work = nullptr;
-        hipEvent_t h2d_done = nullptr, slot_free = nullptr, summ_done = nullptr, tail_taken = nullptr;
-        Chunk ck;
-    } sl[kSlots];
-    char* heads = nullptr;           // head_rlen | head_alen | head_qlen on the device
-    uint32_t* d_flags = nullptr;     // corrupt-record bit, saturated-qlen count
-    uint32_t* summ_host = nullptr;   // pinned: kSlots x 12 summary words | [40] [41] flag words | [48..] kSlots tail descriptors
-    hipStream_t copy_stream = nullptr;
-    IngestKit* kit = nullptr;        // the device's cached streams / events / small buffers, if no other call holds them
-    const size_t head_n = (size_t)(head_records > 0 ? head_records : 1);
-    const size_t inflated_cap = kTailRoom + nb * 65536 + 4096;
-    double unpin_s = 0.0;
-    // What the call allocated goes back when it ends: the pinned staging to its pool at once; the device scratch, events and
-    // streams - 12-15 ms of hipFree / destroy calls, a tenth of a 40 M-record ingest - on a thread of their own
-    // (`background`: the successful end; every stream has been synchronised by then), nobody waits for it.
-    auto release = [&](bool background = false) {
-        std::vector<void*> dev_mem, host_mem;
-        std::vector<hipEvent_t> events;
-        std::vector<hipStream_t> streams;
-        if (kit && !background) {
-            // a call that did not end cleanly: a stream or event of it may be in an error state (a failed copy or kernel), and
-            // a handle kept for the process would hand that state to every later ingest on this device.  Nothing is cached:
-            // the kit's handles are destroyed with the call's own, the next call makes fresh ones.
-            kit->heads = nullptr; kit->heads_bytes = 0;      // (== heads when it was reused: freed below)
-            for (int k = 0; k < kSlots; ++k) {
-                kit->work[k] = nullptr;
-                for (int j = 0; j < 4; ++j) kit->ev[k][j] = nullptr;
-            }
-            kit->copy = nullptr; kit->d_flags = nullptr; kit->summ_host = nullptr;
-            { std::lock_guard<std::mutex> g(kit->mu); kit->busy = false; }
-            kit = nullptr;
-        }
-        for (Slot& q : sl) {
-            const auto t0 = std::chrono::steady_clock::now();
-            g_pinned.give_back(q.pin);
-            unpin_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            for (void* m : {(void*)q.dev, (void*)q.inflated, (void*)q.symbols, (void*)q.offs, (void*)q.words})
-                if (m) dev_mem.push_back(m);
-            if (!kit) {
-                for (hipEvent_t e : {q.h2d_done, q.slot_free, q.summ_done, q.tail_taken})
-                    if (e) events.push_back(e);
-                if (q.work) streams.push_back(q.work);
-            }
-        }
-        if (kit) {                                           // (a call that synchronised cleanly: its handles serve the next one)
-            for (int k = 0; k < kSlots; ++k) {
-                kit->work[k] = sl[k].work;
-                kit->ev[k][0] = sl[k].h2d_done; kit->ev[k][1] = sl[k].slot_free; kit->ev[k][2] = sl[k].summ_done; kit->ev[k][3] = sl[k].tail_taken;
-            }
-            kit->copy = copy_stream;
-            kit->d_flags = d_flags;
-            kit->summ_host = summ_host;
-            if (heads && heads != kit->heads) { kit->heads = heads; kit->heads_bytes = head_n * 10; }
-            std::lock_guard<std::mutex> g(kit->mu);
-            kit->busy = false;
-        } else {
-            if (heads) dev_mem.push_back(heads);
-            if (d_flags) dev_mem.push_back(d_flags);
-            if (summ_host) host_mem.push_back(summ_host);
-            if (copy_stream) streams.push_back(copy_stream);
-        }
-        for (Slot& q : sl) q = Slot();
-        heads = nullptr; d_flags = nullptr; summ_host = nullptr; copy_stream = nullptr;
-        const int device = c->device;
-        auto drop = [device, dev_mem, host_mem, events, streams]() {
-            (void)hipSetDevice(device);
-            for (hipEvent_t e : events) (void)hipEventDestroy(e);
-            for (hipStream_t st : streams) (void)hipStreamDestroy(st);
-            for (void* m : dev_mem) (void)hipFree(m);
-            for (void* m : host_mem) (void)hipHostFree(m);
-        };
-        if (background) g_background.run(drop);
-        else drop();
-    };
-    // All three slots, and their streams, before anything is queued.
-    // The three slots' streams and the copy stream must run beside each other.  The runtime spreads a process's streams
-    // over a handful of hardware queues PER PRIORITY LEVEL, in creation order, together with every other stream of the
-    // process (the context's, the caller's: torch's): two of ours on one queue and chunk j's walk / scan / decode wait
-    // behind chunk j + 1's whole inflate - 1.83 instead of 1.40 s for full-size C3 in a process that had made other
-    // streams before, 1.40 in one that had not.  So the slots' streams are created at the LOWEST priority, a level nobody
-    // else in the process uses (its queues are theirs alone; nothing else runs during an ingest for them to yield to), and
-    // the copy stream at the highest.
-    int prio_low = 0, prio_high = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);
-    double alloc_s = 0.0;
-    if (c->device >= 0 && c->device < 16) {
-        IngestKit& k = g_ingest_kit[c->device];
-        std::lock_guard<std::mutex> g(k.mu);
-        if (!k.busy) { k.busy = true; kit = &k; }
-    }
-
-    auto alloc_slot = [&](int k) -> bool {
-        Slot& q = sl[k];
-        if (q.pin) return true;
-        const auto t0 = std::chrono::steady_clock::now();
-        const bool got = (q.pin = static_cast<char*>(g_pinned.acquire(slot_bytes))) != nullptr &&
-             hipMalloc((void**)&q.dev, slot_bytes) == hipSuccess && hipMalloc((void**)&q.inflated, inflated_cap) == hipSuccess &&
-             hipMalloc((void**)&q.symbols, 4 * bgzf_inflate_symbol_places(inflated_cap, nbw)) == hipSuccess &&
-             hipMalloc((void**)&q.offs, nbw * (size_t)kBamBlockRecs * sizeof(uint16_t)) == hipSuccess &&
-             hipMalloc((void**)&q.words, (nbw * 6 + 12) * sizeof(uint32_t)) == hipSuccess &&
-             (q.work || hipStreamCreateWithPriority(&q.work, hipStreamNonBlocking, prio_low) == hipSuccess) &&
-             (q.h2d_done || hipEventCreateWithFlags(&q.h2d_done, hipEventDisableTiming) == hipSuccess) &&
-             (q.slot_free || hipEventCreateWithFlags(&q.slot_free, hipEventDisableTiming) == hipSuccess) &&
-             (q.summ_done || hipEventCreateWithFlags(&q.summ_done, hipEventDisableTiming) == hipSuccess) &&
-             (q.tail_taken || hipEventCreateWithFlags(&q.tail_taken, hipEventDisableTiming) == hipSuccess);
-        alloc_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return got;
-    };
-    // Slot 0 now; slots 1 and 2 - 2 x (~190 MB pinned + ~0.7 GB of HBM): 90 of the 130 ms a first ingest spent allocating -
-    // on a helper thread while the first chunk is read, uploaded and queued (joined before the second chunk is staged, and
-    // before anything is released).  Their streams are created here, in order: the queue placement above depends on it.
-    if (kit) {                                               // what an earlier call on this device left
-        for (int k = 0; k < kSlots; ++k) {
-            sl[k].work = kit->work[k];
-            sl[k].h2d_done = kit->ev[k][0]; sl[k].slot_free = kit->ev[k][1]; sl[k].summ_done = kit->ev[k][2]; sl[k].tail_taken = kit->ev[k][3];
-        }
-        copy_stream = kit->copy;
-        d_flags = kit->d_flags;
-        summ_host = kit->summ_host;
-        if (kit->heads_bytes >= head_n * 10) heads = kit->heads;
-        else if (kit->heads) { (void)hipFree(kit->heads); kit->heads = nullptr; kit->heads_bytes = 0; }
-    }
-    bool ok = alloc_slot(0);
-    // (every slot's stream AND its four events are made here, on the calling thread: the helper below only allocates memory,
-    // so no handle the queueing code reads - sl[2].tail_taken while chunk 0 is enqueued - is ever written beside it)
-    for (int k = 1; k < kSlots && ok; ++k)
-        ok = (sl[k].work || hipStreamCreateWithPriority(&sl[k].work, hipStreamNonBlocking, prio_low) == hipSuccess) &&
-             (sl[k].h2d_done || hipEventCreateWithFlags(&sl[k].h2d_done, hipEventDisableTiming) == hipSuccess) &&
-             (sl[k].slot_free || hipEventCreateWithFlags(&sl[k].slot_free, hipEventDisableTiming) == hipSuccess) &&
-             (sl[k].summ_done || hipEventCreateWithFlags(&sl[k].summ_done, hipEventDisableTiming) == hipSuccess) &&
-             (sl[k].tail_taken || hipEventCreateWithFlags(&sl[k].tail_taken, hipEventDisableTiming) == hipSuccess);
-    ok = ok && (heads || hipMalloc((void**)&heads, head_n * 10) == hipSuccess) &&
-         (d_flags || hipMalloc((void**)&d_flags, 2 * sizeof(uint32_t)) == hipSuccess) &&
-         (summ_host || hipHostMalloc((void**)&summ_host, 128 * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess) &&
-         (copy_stream || hipStreamCreateWithPriority(&copy_stream, hipStreamNonBlocking, prio_high) == hipSuccess);
-    std::thread alloc_helper;
-    std::atomic<bool> helper_ok(true);
-    double alloc_wait_s = 0.0;                               // (what the calling thread spent waiting for the helper)
-    auto alloc_join = [&]() -> bool {
-        if (alloc_helper.joinable()) {
-            const auto t0 = std::chrono::steady_clock::now();
-            alloc_helper.join();
-            alloc_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
-        return helper_ok.load();
-    };
-    if (ok && map_len - (size_t)f0 > comp_cap / 2) {             // (a file of less than a chunk or so never uses them)
-        const int device = c->device;
-        alloc_helper = std::thread([&, device] {
-            if (hipSetDevice(device) != hipSuccess) { helper_ok = false; return; }
-            for (int k = 1; k < kSlots; ++k)
-                if (!alloc_slot(k)) { helper_ok = false; return; }
-        });
-    }
-    if (!ok) {
-        alloc_join();
-        release();
-        set_error("push_bam_device: cannot allocate the staging / scratch buffers (%zu MB pinned, %zu MB of HBM)",
-                  (kSlots * slot_bytes) >> 20, (kSlots * (slot_bytes + inflated_cap + 4 * bgzf_inflate_symbol_places(inflated_cap, nbw))) >> 20);
-        return BESST_ERR_NOMEM;
-    }
-    double stage_s = 0.0, wait_s = 0.0;
-    int64_t pushed = 0, chunks = 0, comp_total = 0, inflated_total = 0, blocks_total = 0, repaired = 0;
-    size_t fpos = (size_t)f0;
-    double bytes_per_block = first_per_block;
-    rc = BESST_OK;
-    auto hip_fail = [&](hipError_t e) { set_error("push_bam_device: %s", hipGetErrorString(e)); rc = BESST_ERR_HIP; };
-    size_t max_blocks = nb;                                  // (blocks per chunk: fewer for the blocks behind a part's end)
-    bool overhang = false;                                   // the chunk at hand holds the blocks behind the part's end
-    // read chunk j (the next blocks of the file) into slot j % kSlots and start its upload
-    auto stage = [&](int64_t j) -> bool {
-        Slot& q = sl[j % kSlots];
-        if (fpos >= map_len) { q.ck = Chunk(); return true; }   // (nothing left: the slot is not touched)
-        if ((j > 0 && !alloc_join()) || !alloc_slot((int)(j % kSlots))) {
-            set_error("push_bam_device: cannot allocate the staging / scratch buffers (%zu MB pinned, %zu MB of HBM)",
-                      (kSlots * slot_bytes) >> 20, (kSlots * (slot_bytes + inflated_cap + 4 * bgzf_inflate_symbol_places(inflated_cap, nbw))) >> 20);
-            rc = BESST_ERR_NOMEM;
-            return false;
-        }
-        if (j >= kSlots) {                                        // the upload that last read this pinned slot
-            const auto t0 = std::chrono::steady_clock::now();
-            const hipError_t e = hipEventSynchronize(q.h2d_done);
-            wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (e != hipSuccess) { hip_fail(e); return false; }
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        const size_t begin = fpos;
-        q.ck = Chunk();
-        q.ck.first_off = j == 0 ? u0 : 0u;
-        if (begin >= map_len) return true;
-        // A window of the file is READ into the pinned slot by the reader's threads (pread: no page faults, unlike a copy
-        // off the mapping, where the header walk alone touched every page) and the block headers are walked there; the
-        // window is sized from the blocks seen so far, the block it cuts is read again with the next chunk.
-        size_t want = map_len - begin < comp_cap ? map_len - begin : comp_cap;
-        // the first two chunks are short ones - a fifth and a half of a chunk -, so that the chip has something to inflate a
-        // millisecond or two into the call instead of after a whole chunk's read and upload (40 M records, eight calls
-        // each way on one box: 0.119 against 0.125 s); the window of the very first read is sized from the file's first
-        // blocks (bytes_per_block starts at their average)
-        size_t cap_blocks = max_blocks;
-        if (!overhang && j < 2) {
-            cap_blocks = j == 0 ? nb / 5 : nb / 2;
-            if (cap_blocks < 64) cap_blocks = nb < 64 ? nb : 64;
-        }
-        if (bytes_per_block > 0.0) {
-            const size_t guess = (size_t)((double)cap_blocks * bytes_per_block * 1.08) + 65536;
-            if (guess < want) want = guess;
-        }
-        if (!bam_parallel_read(bam, q.pin + desc_bytes, (int64_t)begin, want)) {
-            set_error("push_bam_device: reading the file failed at offset %zu", begin);
-            rc = BESST_ERR_ARG;
-            return false;
-        }
-        size_t used = 0;
-        BgzfBlock* desc = reinterpret_cast<BgzfBlock*>(q.pin);
-        desc[0] = BgzfBlock{0u, 0u, (uint32_t)kTailRoom, 0u, 0u, 0u};   // the tail slot: empty until the chunk before says otherwise
-        if (!scan_bgzf_chunk(reinterpret_cast<const uint8_t*>(q.pin + desc_bytes), want, &used, cap_blocks, comp_cap, desc + 1,
-                             &q.ck.n_blocks, &q.ck.comp, &q.ck.inflated, begin + want < map_len, kTailRoom, true) ||
-            (q.ck.n_blocks == 0 && want > 0)) {
-            set_error("push_bam_device: not a BGZF block at file offset %zu", begin + used);
-            rc = BESST_ERR_UNSUPPORTED;
-            return false;
-        }
-        fpos = begin + q.ck.comp;
-        q.ck.file_end = fpos;
-        bytes_per_block = (double)q.ck.comp / (double)q.ck.n_blocks;
-        stage_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        hipError_t e = hipSuccess;
-        if (j >= kSlots) e = hipStreamWaitEvent(copy_stream, q.slot_free, 0);    // the kernels that last read this device slot
-        if (e == hipSuccess) e = hipMemcpyAsync(q.dev, q.pin, ((size_t)q.ck.n_blocks + 1) * sizeof(BgzfBlock), hipMemcpyHostToDevice, copy_stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(q.dev + desc_bytes, q.pin + desc_bytes, q.ck.comp + 1024, hipMemcpyHostToDevice, copy_stream);
-        if (e == hipSuccess) e = hipEventRecord(q.h2d_done, copy_stream);
-        if (e != hipSuccess) { hip_fail(e); return false; }
-        comp_total += (int64_t)q.ck.comp;
-        inflated_total += (int64_t)q.ck.inflated;
-        blocks_total += q.ck.n_blocks;
-        return true;
-    };
-    // inflate + CRC of the chunk in slot k on the slot's stream (descriptor 0, the tail slot, is empty here: skipped)
-    auto enqueue_inflate = [&](int k) -> bool {
-        Slot& q = sl[k];
-        hipError_t e = hipStreamWaitEvent(q.work, q.h2d_done, 0);
-        // (the chunk two before inflated into this buffer; its tail may still be on its way to the chunk in between)
-        if (e == hipSuccess) e = hipStreamWaitEvent(q.work, q.tail_taken, 0);
-        if (e != hipSuccess) { hip_fail(e); return false; }
-        if (launch_bgzf_inflate(q.work, reinterpret_cast<const uint8_t*>(q.dev + desc_bytes), reinterpret_cast<const BgzfBlock*>(q.dev),
-                                q.ck.n_blocks + 1, q.inflated, q.words, q.symbols)) {
-            rc = BESST_ERR_HIP;
-            return false;
-        }
-        return true;
-    };
-    // where the records of the chunk in slot k begin (entry guesses, walks, verification, scan), its summary on the way to the
-    // host.  tail_len bytes at `tail_at` of the buffer of the slot BEFORE are the record the chunk before did not finish: they
-    // are copied in front of this chunk's first block and become its block 0.  first_entry: where the first record begins
-    // in block 1 when there is no tail (the end of the header in the file's first chunk, else 0).
-    const int32_t n_ref = besst_bam_n_references(bam);
-    auto enqueue_walk = [&](int k, uint64_t tail_at, uint32_t tail_len, uint32_t forced_block, uint32_t forced_entry, uint32_t mode) -> bool {
-        Slot& q = sl[k];
-        Slot& other = sl[(k + kSlots - 1) % kSlots];
-        uint32_t* w = q.words;
-        hipError_t e = hipSuccess;
-        if (tail_len) {
-            BgzfBlock* patch = reinterpret_cast<BgzfBlock*>(summ_host + 48) + k;
-            *patch = BgzfBlock{0u, 0u, (uint32_t)(kTailRoom - tail_len), 0u, tail_len, 0u};
-            e = hipMemcpyAsync(q.dev, patch, sizeof(BgzfBlock), hipMemcpyHostToDevice, q.work);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(q.inflated + kTailRoom - tail_len, other.inflated + tail_at, tail_len, hipMemcpyDeviceToDevice, q.work);
-        }
-        if (e == hipSuccess && other.tail_taken) e = hipEventRecord(other.tail_taken, q.work);   // (a slot no chunk has used yet has no buffer to protect)
-        if (e != hipSuccess) { hip_fail(e); return false; }
-        if (launch_bam_walk_scan(q.work, q.inflated, reinterpret_cast<const BgzfBlock*>(q.dev), q.ck.n_blocks + 1,
-                                 (uint64_t)kTailRoom + q.ck.inflated, n_ref, tail_len ? 0xffffffffu : forced_block, forced_entry, mode, w, q.offs,
-                                 w + nbw, w + 2 * nbw, w + 3 * nbw, w + 4 * nbw, w + 5 * nbw, w + 6 * nbw)) {
-            rc = BESST_ERR_HIP;
-            return false;
-        }
-        e = hipMemcpyAsync(summ_host + 12 * k, w + 6 * nbw, 12 * sizeof(uint32_t), hipMemcpyDeviceToHost, q.work);
-        if (e == hipSuccess) e = hipEventRecord(q.summ_done, q.work);
-        if (e != hipSuccess) { hip_fail(e); return false; }
-        return true;
-    };
-    BamColumns col{};
-    col.head_rlen = reinterpret_cast<int32_t*>(heads);
-    col.head_alen = reinterpret_cast<int32_t*>(heads + head_n * 4);
-    col.head_qlen = reinterpret_cast<uint16_t*>(heads + head_n * 8);
-    {
-        hipError_t e = hipMemsetAsync(d_flags, 0, 2 * sizeof(uint32_t), c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(heads, 0, head_n * 10, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the slots' streams start behind these
-        if (e != hipSuccess) hip_fail(e);
-    }
-    // where the first chunk's first record begins: the end of the header / the first byte of a part of a file in htslib's
-    // layout; a slice behind the first one: where the caller says (the bytes in front belong to the last record of the slice
-    // before), or a guess that the caller will check against what the slice before reports
-    const double setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-    uint32_t fb0 = 1u, fe0 = u0, mode0 = 0u;
-    int64_t no_start_left = -1;                              // >= 0: a slice no record begins in; so many bytes of the record before lie behind it
-    if (rc == BESST_OK && stage(0) && sl[0].ck.n_blocks) {
-        if (slice && part > 0 && first_skip < 0) {
-            fb0 = 0xffffffffu; fe0 = 0u; mode0 = kWalkFirstGuessed;
-        } else if (slice && part > 0) {
-            const BgzfBlock* desc = reinterpret_cast<const BgzfBlock*>(sl[0].pin);
-            uint64_t skip = (uint64_t)first_skip;
-            fb0 = 0u;
-            for (uint32_t i = 1; i <= sl[0].ck.n_blocks; ++i) {
-                if (skip < desc[i].dst_len) { fb0 = i; fe0 = (uint32_t)skip; break; }
-                skip -= desc[i].dst_len;
-            }
-            if (fb0 == 0u && fpos >= map_len) {
-                // the WHOLE slice lies in this chunk and no record begins in it (its blocks are the tail of the record before -
-                // or hold nothing: the EOF marker of a file with fewer blocks than ranks): an empty slice, what comes in goes on
-                no_start_left = (int64_t)skip;
-                sl[0].ck = Chunk();
-            } else if (fb0 == 0u) {
-                set_error("push_bam_device: the slice's first record begins behind its first chunk (%lld bytes in)", (long long)first_skip);
-                rc = BESST_ERR_UNSUPPORTED;
-            }
-        }
-        if (rc == BESST_OK && sl[0].ck.n_blocks && enqueue_inflate(0) && enqueue_walk(0, 0, 0u, fb0, fe0, mode0) && stage(1) && sl[1].ck.n_blocks)
-            enqueue_inflate(1);
-    }
-    int64_t first_at = -1, carry_out = 0, over_bytes = 0;    // (the slice form's answers)
-    for (int64_t j = 0; rc == BESST_OK && sl[j % kSlots].ck.n_blocks; ++j) {
-        Slot& q = sl[j % kSlots];
-        Slot& nx = sl[(j + 1) % kSlots];
-        // chunk j + 2: read, uploaded and queued behind chunk j + 1's inflate while chunk j's count is on its way (with two
-        // slots the inflate of chunk j + 2 could not be queued before chunk j's verdict had been seen AND the file read:
-        // the chip idled between two inflates whenever the two took longer than one inflate)
-        if (nx.ck.n_blocks) {
-            if (!stage(j + 2)) break;
-            if (sl[(j + 2) % kSlots].ck.n_blocks && !enqueue_inflate((int)((j + 2) % kSlots))) break;
-        }
-        {
-            const auto t0 = std::chrono::steady_clock::now();
-            const hipError_t e = hipEventSynchronize(q.summ_done);
-            wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (e != hipSuccess) { hip_fail(e); break; }
-        }
-        const uint32_t* sm = summ_host + 12 * (j % kSlots);
-        if (!sm[1]) {
-            if (sm[3]) set_error("push_bam_device: block %u of chunk %lld did not inflate on the device (status %u)", sm[2] ? sm[2] - 1u : 0u, (long long)j, sm[3]);
-            else set_error("push_bam_device: the records of chunk %lld could not be located on the device (block %u: a record start "
-                           "that its neighbours do not confirm, or a corrupt length)", (long long)j, sm[2] ? sm[2] - 1u : 0u);
-            rc = BESST_ERR_UNSUPPORTED;
-            break;
-        }
-        if (parts > 1 && sm[7] && !slice) {
-            set_error("push_bam_device: a record straddles BGZF blocks (chunk %lld): a part of such a file cannot be cut at a block", (long long)j);
-            rc = BESST_ERR_UNSUPPORTED;
-            break;
-        }
-        const uint32_t tail_len = sm[4];
-        if (tail_len > (uint32_t)kTailRoom) {
-            set_error("push_bam_device: a record of more than %zu MB", kTailRoom >> 20);
-            rc = BESST_ERR_UNSUPPORTED;
-            break;
-        }
-        if (j == 0) {
-            const uint64_t at = (uint64_t)sm[8] | ((uint64_t)sm[9] << 32);
-            first_at = at == ~0ull ? -1 : (int64_t)(at - (uint64_t)kTailRoom);
-            if (slice && first_at < 0) {
-                set_error("push_bam_device: no record begins in the first chunk of the slice");
-                rc = BESST_ERR_UNSUPPORTED;
-                break;
-            }
-        }
-        if (overhang) {                                      // bytes of the slice's last record that lie in the next slice
-            if (tail_len) over_bytes += (int64_t)q.ck.inflated;              // (all of this chunk, and the record goes on)
-            else carry_out = over_bytes + (int64_t)sm[8];
-        }
-        if (nx.ck.n_blocks) {
-            // chunk j + 1's records can be located now: it starts with chunk j's unfinished record, if there is one
-            if (!enqueue_walk((int)((j + 1) % kSlots), (uint64_t)sm[5] | ((uint64_t)sm[6] << 32), tail_len, 1u, 0u, 0u)) break;
-        } else if (tail_len && slice && (overhang ? fpos < whole_file : map_len < whole_file)) {
-            // the slice's last record runs on behind the slice's end: the blocks that follow are inflated for its bytes (and for
-            // nothing else: the records that begin in them are the next slice's) - chunk after chunk until the record ends
-            // (a few blocks at first - a record seldom runs over more than one or two -, four times as many while it goes on: the
-            // blocks belong to the next slice, and a damaged one among them is that slice's to report)
-            max_blocks = overhang ? (max_blocks * 4 < nb ? max_blocks * 4 : nb) : (nb < 64 ? nb : 64);
-            overhang = true;
-            map_len = whole_file;
-            sl[(j + 2) % kSlots].ck = Chunk();
-            if (!stage(j + 1)) break;
-            if (!nx.ck.n_blocks) { set_error("push_bam_device: the file ends inside a record"); rc = BESST_ERR_ARG; break; }
-            if (!enqueue_inflate((int)((j + 1) % kSlots))) break;
-            if (!enqueue_walk((int)((j + 1) % kSlots), (uint64_t)sm[5] | ((uint64_t)sm[6] << 32), tail_len, 0xffffffffu, 0u, kWalkOverhang)) break;
-        } else if (tail_len) {
-            set_error("push_bam_device: the %s ends inside a record", parts > 1 ? "part of the file" : "file");
-            rc = parts > 1 ? BESST_ERR_UNSUPPORTED : BESST_ERR_ARG;
-            break;
-        }
-        const int64_t got = (int64_t)sm[0];
-        repaired += (int64_t)sm[2];
-        const int64_t have = c->n_records + pushed;
-        if (have + got >= ((int64_t)1 << 32)) { set_error("more than 2^32-1 records in one context"); rc = BESST_ERR_ARG; break; }
-        if ((size_t)(have + got) > c->tid.cap) {
-            // room for the whole file at the rate of the bytes read so far (+ 6 %), at least for this chunk; the decode of
-            // the chunk before may still be writing the columns that are about to move
-            int64_t want = have + got;
-            const size_t at = q.ck.file_end;                 // end of chunk j in the file
-            if (at > (size_t)f0 && at < map_len)
-                want = c->n_records + (int64_t)((double)(pushed + got) * ((double)(map_len - (size_t)f0) / (double)(at - (size_t)f0)) * 1.06) + 4096;
-            if (want < have + got) want = have + got;
-            if (want >= ((int64_t)1 << 32)) want = ((int64_t)1 << 32) - 1;
-            const auto t0 = std::chrono::steady_clock::now();
-            hipError_t e = hipSuccess;
-            for (Slot& o : sl)                               // (slot_free: behind a slot's last decode)
-                if (e == hipSuccess && o.slot_free) e = hipEventSynchronize(o.slot_free);
-            wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (e != hipSuccess) { hip_fail(e); break; }
-            const int64_t keep = c->n_records;
-            c->n_records = have;
-            rc = reserve_records(c, want);
-            c->n_records = keep;
-            if (rc) break;
-        }
-        col.tid = c->tid.p; col.mtid = c->mtid.p; col.pos = c->pos.p; col.mpos = c->mpos.p; col.tlen = c->tlen.p;
-        col.flag = c->flag.p; col.qlen = c->qlen.p; col.mapq = c->mapq.p;
-        if (launch_bam_decode(q.work, q.inflated, reinterpret_cast<const BgzfBlock*>(q.dev), q.ck.n_blocks + 1, q.offs, q.words + nbw,
-                              q.words + 3 * nbw, col, have, pushed, head_records, d_flags)) { rc = BESST_ERR_HIP; break; }
-        const hipError_t e = hipEventRecord(q.slot_free, q.work);
-        if (e != hipSuccess) { hip_fail(e); break; }
-        pushed += got;
-        ++chunks;
-    }
-    const auto tw = std::chrono::steady_clock::now();
-    hipError_t e0 = hipSuccess, e1 = hipSuccess;
-    for (Slot& q : sl) {
-        if (!q.work) continue;
-        const hipError_t e = hipStreamSynchronize(q.work);
-        if (e != hipSuccess) e0 = e;
-    }
-    const hipError_t ec = hipStreamSynchronize(copy_stream);
-    if (rc == BESST_OK && (e0 != hipSuccess || e1 != hipSuccess || ec != hipSuccess)) hip_fail(e0 != hipSuccess ? e0 : e1 != hipSuccess ? e1 : ec);
-    if (rc == BESST_OK) {
-        hipError_t e = hipMemcpyAsync(summ_host + 40, d_flags, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        const int64_t hn = pushed < head_records ? pushed : head_records;
-        if (e == hipSuccess && hn > 0) {
-            e = hipMemcpyAsync(head_rlen, col.head_rlen, (size_t)hn * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(head_alen, col.head_alen, (size_t)hn * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(head_qlen, col.head_qlen, (size_t)hn * 2, hipMemcpyDeviceToHost, c->stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) hip_fail(e);
-    }
-    wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
-    if (rc == BESST_OK && (summ_host[40] & 1u)) {
-        set_error("push_bam_device: corrupt record (its name and CIGAR do not fit its length)");
-        rc = BESST_ERR_ARG;
-    }
-    const uint32_t saturated = rc == BESST_OK ? summ_host[41] : 0u;
-    const auto t_rel = std::chrono::steady_clock::now();
-    alloc_join();
-    release(rc == BESST_OK);
-    if (const char* e = getenv("BESST_INGEST_PROFILE"); e && atoi(e))
-        fprintf(stderr, "[push_bam_device] setup %.3f s  alloc %.3f s (%.3f of it waited for)  staging %.3f s  waiting %.3f s  release %.3f s (unpinning %.3f)  total %.3f s\n", setup_s, alloc_s, alloc_wait_s, stage_s,
-                wait_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_rel).count(), unpin_s,
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count());
-    if (rc) return rc;
-    c->n_records += pushed;
-    c->built = false;
-    bam_mark_consumed(bam, (int64_t)saturated);
-    if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        stats->records = pushed;
-        stats->chunks = chunks;
-        stats->bytes_h2d = comp_total;
-        stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-        stats->decode_seconds = stage_s;
-        stats->copy_wait_seconds = wait_s;
-        stats->inflated_bytes = inflated_total;
-        stats->blocks = blocks_total;
-        stats->on_device = 1;
-        stats->starts_repaired = (int32_t)(repaired > 0x7fffffff ? 0x7fffffff : repaired);
-    }
-    if (boundary) {
-        if (chunks == 0 && first_at < 0) {                   // a slice without a block (more ranks than blocks): what comes in goes out
-            first_at = first_skip > 0 ? first_skip : 0;
-            carry_out = no_start_left >= 0 ? no_start_left : first_at;
-        }
-        boundary[0] = first_at;
-        boundary[1] = carry_out;
-    }
-    return BESST_OK;
-}
-}  // namespace
-
-int besst_ctx_push_bam_device_part(besst_ctx* c, besst_bam* bam, int32_t part, int32_t parts, int64_t chunk_blocks, int64_t head_records,
-                                   int32_t* head_rlen, int32_t* head_alen, uint16_t* head_qlen, besst_ingest_stats* stats) {
-    return push_bam_device_impl(c, bam, part, parts, chunk_blocks, head_records, head_rlen, head_alen, head_qlen, stats, -1, nullptr);
-}
-
-// Slice `part` of `parts` of a file in ANY block layout (multi-GPU ingest of files whose records straddle BGZF blocks): the
-// slices are cut at block boundaries as above, and a record belongs to the slice it BEGINS in.  Where a slice's first record
-// begins is the one thing a rank cannot know alone: first_skip < 0 lets it guess (the heuristics of the block-to-block
-// verification; everything behind the guess is verified as usual), and boundary[0] reports the offset used - in inflated
-// bytes from the slice's first block -, boundary[1] how many bytes of the slice's last record lie in the next slice.  The
-// callers exchange these two numbers: slice r is right iff boundary[0] of slice r equals boundary[1] of slice r - 1 (slice 0
-// begins behind the header and is always right); a slice whose guess was wrong is read again with first_skip = that
-// number (besst_amd.distributed.ingest_slice does this).  The bytes of a slice's last record that lie behind its end are
-// read from the blocks that follow (at most 4 MiB).
-int besst_ctx_push_bam_device_slice(besst_ctx* c, besst_bam* bam, int32_t part, int32_t parts, int64_t chunk_blocks, int64_t first_skip,
-                                    int64_t* boundary, int64_t head_records, int32_t* head_rlen, int32_t* head_alen,
-                                    uint16_t* head_qlen, besst_ingest_stats* stats) {
-    BESST_REQUIRE(boundary, "push_bam_device_slice: boundary is null");
-    return push_bam_device_impl(c, bam, part, parts, chunk_blocks, head_records, head_rlen, head_alen, head_qlen, stats, first_skip,
-                                boundary);
-}
-
-int besst_bgzf_inflate_device(int device, const void* bgzf, size_t n_bytes, void* out, size_t out_cap, size_t* out_len) {
-    BESST_REQUIRE(bgzf && out_len && (out || out_cap == 0), "bgzf_inflate_device: null pointer");
-    BESST_HIP_TRY(hipSetDevice(device));
-    const uint8_t* map = static_cast<const uint8_t*>(bgzf);
-    size_t nb = 4096;                                        // (BESST_INFLATE_HOOK_BLOCKS: blocks per launch, for timing runs)
-    if (const char* e = getenv("BESST_INFLATE_HOOK_BLOCKS"); e && atoi(e) > 0) nb = (size_t)atoi(e);
-    const size_t comp_cap = nb * 65536;
-    std::vector<BgzfBlock> desc(nb);
-    std::vector<uint32_t> status(nb);
-    std::vector<uint8_t> host;
-    char* d_comp = nullptr;
-    uint8_t* d_inf = nullptr;
-    BgzfBlock* d_desc = nullptr;
-    uint32_t* d_status = nullptr;
-    uint32_t* d_sym = nullptr;
-    auto release = [&]() {
-        if (d_comp) (void)hipFree(d_comp);
-        if (d_inf) (void)hipFree(d_inf);
-        if (d_sym) (void)hipFree(d_sym);
-        if (d_desc) (void)hipFree(d_desc);
-        if (d_status) (void)hipFree(d_status);
-    };
-    size_t fpos = 0, written = 0, block0 = 0;
-    int rc = BESST_OK;
-    while (fpos < n_bytes && rc == BESST_OK) {
-        const size_t begin = fpos;
-        uint32_t n = 0;
-        size_t comp = 0, inflated = 0;
-        if (!scan_bgzf_chunk(map, n_bytes, &fpos, nb, comp_cap, desc.data(), &n, &comp, &inflated)) {
-            set_error("bgzf_inflate_device: not a BGZF block at offset %zu", fpos);
-            rc = BESST_ERR_ARG;
-            break;
-        }
-        if (n == 0) break;
-        release();
-        d_comp = nullptr; d_inf = nullptr; d_desc = nullptr; d_status = nullptr; d_sym = nullptr;
-        hipError_t e = hipMalloc((void**)&d_comp, comp + 4096);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_inf, inflated + 4096);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_sym, 4 * bgzf_inflate_symbol_places(inflated + 4096, n));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_desc, (size_t)n * sizeof(BgzfBlock));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_status, (size_t)n * 4);
-        if (e == hipSuccess) e = hipMemset(d_comp + comp, 0, 4096);
-        if (e == hipSuccess) e = hipMemcpy(d_comp, map + begin, comp, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_desc, desc.data(), (size_t)n * sizeof(BgzfBlock), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { set_error("bgzf_inflate_device: %s", hipGetErrorString(e)); rc = BESST_ERR_HIP; break; }
-        if ((rc = launch_bgzf_inflate(nullptr, reinterpret_cast<const uint8_t*>(d_comp), d_desc, n, d_inf, d_status, d_sym))) break;
-        host.resize(inflated);
-        e = hipMemcpy(status.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && inflated) e = hipMemcpy(host.data(), d_inf, inflated, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { set_error("bgzf_inflate_device: %s", hipGetErrorString(e)); rc = BESST_ERR_HIP; break; }
-        for (uint32_t b = 0; b < n; ++b) {
-            if (status[b]) {
-                set_error("bgzf_inflate_device: block %zu did not inflate (status %u)", block0 + b, status[b]);
-                rc = BESST_ERR_UNSUPPORTED;
-                break;
-            }
-            if (written + desc[b].dst_len > out_cap) { set_error("bgzf_inflate_device: output buffer too small"); rc = BESST_ERR_ARG; break; }
-            memcpy(static_cast<uint8_t*>(out) + written, host.data() + (((size_t)desc[b].dst_off_hi << 32) | desc[b].dst_off_lo), desc[b].dst_len);
-            written += desc[b].dst_len;
-        }
-        block0 += n;
-    }
-    release();
-    if (rc) return rc;
-    *out_len = written;
     return BESST_OK;
 }
 

@@ -711,7 +711,7 @@ int besst_bam_write_records(const char* path, int64_t n_ref, const char* const* 
 }  // extern "C"
 
 namespace besst {
-// for besst_ctx_push_bam (api.hip): how far the reader is through its file
+// for besst_ctx_push_bam (ingest.hip): how far the reader is through its file
 int64_t bam_file_bytes(besst_bam* b) { return b ? (int64_t)b->map_len : 0; }
 int64_t bam_file_position(besst_bam* b) { return b ? (int64_t)b->file_off : 0; }
 

@@ -10,7 +10,7 @@ out="${here}/../libbesst_amd.so"
 obj="${here}/_build"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result ${BESST_EXTRA_FLAGS:-}"
-SRCS="api classify sortreduce onesweep runs metrics score bam_reader bgzf_gpu hostmath linearize chain scorepaths emit fasta emit_text"
+SRCS="api classify sortreduce onesweep runs metrics score bam_reader bgzf_gpu hostmath linearize chain scorepaths emit fasta emit_text ingest"
 mkdir -p "${obj}"
 stamp="${obj}/flags.txt"
 if [ ! -f "${stamp}" ] || [ "$(cat "${stamp}")" != "${FLAGS}" ]; then
@@ -21,7 +21,11 @@ pids=()
 for f in ${SRCS}; do
     src="${here}/${f}.hip"
     o="${obj}/${f}.o"
-    if [ ! -f "${o}" ] || [ "${src}" -nt "${o}" ] || [ "${here}/common.h" -nt "${o}" ] || [ "${here}/../../include/besst_amd.h" -nt "${o}" ]; then
+    stale=0
+    for dep in "${src}" "${here}"/*.h "${here}/../../include/besst_amd.h"; do
+        if [ ! -f "${o}" ] || [ "${dep}" -nt "${o}" ]; then stale=1; fi
+    done
+    if [ "${stale}" = 1 ]; then
         "${HIPCC}" ${FLAGS} -c "${src}" -o "${o}" &
         pids+=($!)
     fi

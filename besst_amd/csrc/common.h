@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/besst_amd.h"
+#include "bgzf_scan.h"
 
 namespace besst {
 
@@ -29,7 +30,7 @@ void set_error(const char* fmt, ...);
         }                                        \
     } while (0)
 
-// ---- the BAM reader's position in its file (bam_reader.hip), for the streamed ingest of api.hip
+// ---- the BAM reader's position in its file (bam_reader.hip), for the streamed ingest of ingest.hip
 }  // namespace besst
 struct besst_bam;
 namespace besst {
@@ -43,11 +44,7 @@ bool bam_parallel_read(besst_bam* b, void* dst, int64_t file_off, size_t bytes);
 void bam_mark_consumed(besst_bam* b, int64_t saturated_qlen);
 
 // ---- BAM ingest on the GPU (bgzf_gpu.hip) ---------------------------------------------------------------
-struct BgzfBlock {             // one BGZF block of a chunk: its DEFLATE payload in the chunk's compressed bytes, its place in
-    uint32_t src_off, src_len; // the chunk's inflated scratch (256-byte aligned) and ISIZE
-    uint32_t dst_off_lo, dst_off_hi;
-    uint32_t dst_len, crc;     // and the CRC-32 of the inflated bytes from the gzip trailer
-};
+// (BgzfBlock, a chunk's block descriptor: bgzf_scan.h)
 constexpr int kBamBlockRecs = 2048;   // a 64 KiB block holds < 65536 / 36 records
 struct BamColumns {
     int32_t *tid, *mtid, *pos, *mpos, *tlen;
@@ -200,8 +197,6 @@ constexpr int kRadix = 1 << kRadixBits;
 constexpr int kRedThreads = 256;
 constexpr int kRedItems = 8;
 constexpr int kRedTile = kRedThreads * kRedItems;      // 2048 tuples per block
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 struct CEDelta {
     int count, too_long, dup, nus;

@@ -459,7 +459,9 @@ def test_long_reads_cover_blocks_and_chunks_whole():
 
 def test_a_file_that_ends_inside_a_record_is_an_error():
     """A straddling file cut off behind a block in the middle of a record (and closed with an EOF marker): the device form
-    reports it (BESST_ERR_ARG: corrupt input, not an unsupported form) and appends nothing."""
+    reports it (BESST_ERR_ARG: corrupt input, not an unsupported form) and appends nothing.  The refused call leaves nothing
+    behind for the process: a good file ingested afterwards on the same device - with handles the ingest has to make afresh -
+    and once more - with the handles that call cached - gives the host reader's columns."""
     batch = _library(2000)
     with tempfile.TemporaryDirectory() as tmp:
         path, cut = os.path.join(tmp, 'x.bam'), os.path.join(tmp, 'cut.bam')
@@ -475,6 +477,18 @@ def test_a_file_that_ends_inside_a_record_is_an_error():
         with pytest.raises(_lib.BesstDeviceError) as e:
             bamio.ResidentBam(cut, threads=2, mode='device')
         assert 'ends inside a record' in str(e.value)
+        good = _library(3000)
+        assert len(good) == 6000
+        path = os.path.join(tmp, 'good.bam')
+        bamio.write_bam(path, good, threads=2, level=1)
+        host = bamio.read_bam(path, threads=2)
+        for _ in range(2):
+            bam = bamio.ResidentBam(path, threads=2, mode='device')
+            try:
+                assert bam.ingest.on_device == 1
+                _check_against_host(path, bam, host)
+            finally:
+                bam.close()
 
 
 @pytest.mark.parametrize('block_bytes,world,decoys,chunk_blocks', [(5000, 2, False, 0), (5000, 5, False, 64), (700, 3, False, 64),

@@ -9,7 +9,7 @@ mkdir -p "${out}"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result ${flags} \
     -c "${src}/${file}.hip" -o "${out}/${file}_${name}.o"
 objs=""
-for f in api classify sortreduce onesweep runs metrics score bam_reader bgzf_gpu hostmath linearize chain scorepaths; do
+for f in api classify sortreduce onesweep runs metrics score bam_reader bgzf_gpu hostmath linearize chain scorepaths emit fasta emit_text ingest; do
     if [ "$f" = "${file}" ]; then objs="${objs} ${out}/${file}_${name}.o"; else objs="${objs} ${obj}/${f}.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC ${objs} -lz -ldl -lpthread -o "${out}/libbesst_amd_${name}.so"
