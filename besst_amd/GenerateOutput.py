@@ -8,6 +8,8 @@ they DELETE the removed contigs from the caller's dicts.
 :class:`SequenceStore` in HBM for the whole run, ``seq_overlap_kernel`` finds the overlaps of the junctions that may
 merge, the host turns placements + overlaps into a piece table with numpy, and ``emit_kernel`` gathers the FASTA bytes
 (copy / reverse-complement / 'N' fill) in chunks that are copied back and written while the next chunk is produced.
+With ``param.outputs_bgzf`` the chunks are compressed on the device first (csrc/bgzf_deflate.hip) and the file is
+``Scaffolds-pass<n>.fa.gz``, a BGZF file: only the compressed bytes cross PCIe.
 AGP and GFF are plain text from names, positions and gaps: on the host by default, and with ``param.outputs_on_gpu`` formatted
 on the device from flat columns and the store's name pool (csrc/emit_text.hip).  A store with ``batch_fasta`` set also
 writes ``repeats.fa`` / ``low_coverage_contigs.fa`` from the pool with one kernel instead of one fetch per contig.
@@ -132,6 +134,8 @@ TEXT_AGP, TEXT_GFF = 0, 1
 TEXT_INFO_WORDS = 3                      # include/besst_amd.h: BESST_TEXT_INFO_WORDS
 TEXT_LIMIT = 1 << 62                     # positions and lengths of this magnitude or more are left to the host writer
 FASTA_LINE = 60                          # bases per line of repeats.fa / low_coverage_contigs.fa
+BGZF_BLOCK_PAYLOAD = 65280               # include/besst_amd.h: BESST_BGZF_BLOCK_PAYLOAD (htslib's); read where it is used
+BGZF_EOF = bytes(bytearray([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0]))
 last_timings = {}                        # PrintOutput's wall-time split of its latest call (seconds)
 
 
@@ -670,19 +674,29 @@ def _report(em, param):
         raise bad[1]
 
 
-def scaffold_bytes(F, param, store=None, unique_id=None, chunk_bytes=None):
-    """The FASTA text PrintOutput would write, as bytes (``chunk_bytes``: produced in ranges of that many bytes)."""
+def scaffold_bytes(F, param, store=None, unique_id=None, chunk_bytes=None, bgzf=False):
+    """The FASTA text PrintOutput would write, as bytes (``chunk_bytes``: produced in ranges of that many bytes).  ``bgzf``:
+    the BGZF file PrintOutput writes with ``param.outputs_bgzf`` instead (ranges of whole blocks within ``chunk_bytes``)."""
     em = _Emitter(F, param, store, unique_id)
     try:
         torch, total = em.torch, em.total
         step = total if not chunk_bytes else int(chunk_bytes)
+        if bgzf:
+            step = _bgzf_chunk(step)
         parts = []
         with torch.cuda.device(em.dev):
-            buf = torch.empty(max(16, (min(step, total) + 15) // 16 * 16), dtype=torch.uint8, device=em.dev)
-            for begin in range(0, total, max(step, 1)):
+            buf = torch.empty(max(16, (min(step, total) + 15) // 16 * 16) + (EMIT_PAD if bgzf else 0), dtype=torch.uint8,
+                              device=em.dev)            # (the compressor reads whole words: up to 3 bytes behind its input)
+            press = _Deflater(torch, em.dev, min(step, total)) if bgzf else None
+            for begin in (range(0, total, max(step, 1)) if total or not bgzf else [0]):
                 end = min(total, begin + step)
-                em.emit(begin, end, buf)
-                parts.append(buf[:end - begin].cpu().numpy().tobytes())
+                if end > begin:
+                    em.emit(begin, end, buf)
+                if bgzf:
+                    press.run(buf, end - begin, end == total)
+                    parts.append(press.out[:int(press.length.item())].cpu().numpy().tobytes())
+                else:
+                    parts.append(buf[:end - begin].cpu().numpy().tobytes())
         _report(em, param)
         return b''.join(parts)
     finally:
@@ -808,6 +822,113 @@ class _ByteSource(object):
         self.torch, self.dev, self.total, self.emit = torch, dev, total, emit
 
 
+def _bgzf_chunk(chunk_bytes):
+    """The largest multiple of the block payload within ``chunk_bytes`` (one block at least): chunks cut there leave every
+    block of a file but its last full."""
+    payload = int(BGZF_BLOCK_PAYLOAD)
+    return max(1, int(chunk_bytes) // payload) * payload
+
+
+class _Deflater(object):
+    """Device buffers of one BGZF compression of up to ``cap`` bytes (csrc/bgzf_deflate.hip): workspace, output, length."""
+
+    def __init__(self, torch, dev, cap):
+        self.torch, self.dev, self.lib = torch, dev, _lib.load()
+        self.payload = int(BGZF_BLOCK_PAYLOAD)
+        self.cap = int(cap)
+        self.bound = self.lib.besst_dev_bgzf_deflate_bound(self.cap, self.payload, 1)
+        self.ws_bytes = self.lib.besst_dev_bgzf_deflate_workspace_bytes(self.cap, self.payload)
+        if not self.ws_bytes:
+            raise ValueError('BGZF_BLOCK_PAYLOAD must lie in 1..65280')
+        self._ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.out = torch.empty(self.bound + 16, dtype=torch.uint8, device=dev)
+        self.length = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def run(self, src, n, eof, stream=None):
+        """Enqueue: the first ``n`` bytes of the uint8 device tensor ``src`` -> ``self.out`` / ``self.length``."""
+        if n > self.cap:
+            raise ValueError('more bytes than the buffers were made for')
+        if stream is None:
+            stream = self.torch.cuda.current_stream(self.dev)
+        p = _C.c_void_p
+        _lib.check(self.lib.besst_dev_bgzf_deflate(p(stream.cuda_stream), p(src.data_ptr()), int(n), self.payload, 1 if eof else 0,
+                                                   p(self._ws.data_ptr()), self.ws_bytes, p(self.out.data_ptr()), self.bound,
+                                                   p(self.length.data_ptr()), None), 'besst_dev_bgzf_deflate')
+
+
+def bgzf_compress(data, block_payload=None, eof=True, device=0):
+    """``data`` (bytes-like) as a BGZF file, compressed on the device through the library's host hook
+    (besst_bgzf_deflate_device).  ``block_payload``: input bytes per block, BGZF_BLOCK_PAYLOAD by default; ``eof``: the
+    28-byte EOF block is appended."""
+    payload = int(BGZF_BLOCK_PAYLOAD if block_payload is None else block_payload)
+    lib = _lib.load()
+    raw = np.frombuffer(bytes(data), dtype=np.uint8)
+    bound = lib.besst_dev_bgzf_deflate_bound(int(raw.shape[0]), payload, 1 if eof else 0)
+    if not 1 <= payload <= 65280:
+        raise ValueError('block_payload must lie in 1..65280')
+    out = np.empty(max(1, bound), dtype=np.uint8)
+    n = _C.c_size_t(0)
+    _lib.check(lib.besst_bgzf_deflate_device(int(device), _lib.ptr(raw) if raw.shape[0] else None, int(raw.shape[0]), payload,
+                                             1 if eof else 0, _lib.ptr(out), int(bound), _C.byref(n)), 'besst_bgzf_deflate_device')
+    return out[:n.value].tobytes()
+
+
+def _write_bgzf_chunks(src, path, chunk_bytes, eof=True):
+    """The compressed sibling of _write_fasta_chunks: emit -> device buffer -> BGZF blocks on the device -> pinned buffer ->
+    file, two of each.  A chunk is a whole number of blocks; the kernels of chunk c + 1 are enqueued before the length of
+    chunk c is waited for, and only the compressed bytes are copied back.
+    -> seconds spent in (emit kernels, deflate kernels, copies, file writes), bytes written"""
+    torch, dev, total = src.torch, src.dev, src.total
+    chunk = _bgzf_chunk(chunk_bytes)
+    size = min(chunk, max(total, 1))
+    t_kernel = t_deflate = t_copy = t_write = 0.0
+    written = 0
+    with torch.cuda.device(dev), open(path, 'wb') as fh:
+        d_buf = [torch.empty((size + 15) // 16 * 16 + EMIT_PAD, dtype=torch.uint8, device=dev) for _ in range(2)]
+        press = [_Deflater(torch, dev, size) for _ in range(2)]
+        h_buf = [torch.empty(press[0].bound, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        h_len = [torch.zeros(1, dtype=torch.int64).pin_memory() for _ in range(2)]
+        compute, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+
+        def drain(slot, ev):
+            nonlocal t_kernel, t_deflate, t_copy, t_write, written
+            ev[3].synchronize()                                  # the chunk's length is on the host
+            n = int(h_len[slot][0])
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(copy):
+                c0.record(copy)
+                h_buf[slot][:n].copy_(press[slot].out[:n], non_blocking=True)
+                c1.record(copy)
+            c1.synchronize()
+            t_kernel += ev[0].elapsed_time(ev[1]) * 1e-3
+            t_deflate += ev[1].elapsed_time(ev[2]) * 1e-3
+            t_copy += c0.elapsed_time(c1) * 1e-3
+            t0 = time.time()
+            fh.write(memoryview(h_buf[slot].numpy())[:n])
+            t_write += time.time() - t0
+            written += n
+
+        before = None
+        for i, begin in enumerate(range(0, total, chunk) if total else [0]):
+            end, slot = min(total, begin + chunk), i % 2
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] + [torch.cuda.Event()]
+            ev[0].record(compute)
+            if end > begin:
+                src.emit(begin, end, d_buf[slot], compute)
+            ev[1].record(compute)
+            press[slot].run(d_buf[slot], end - begin, eof and end == total, compute)
+            ev[2].record(compute)
+            copy.wait_event(ev[2])
+            with torch.cuda.stream(copy):
+                h_len[slot].copy_(press[slot].length, non_blocking=True)
+                ev[3].record(copy)
+            if before is not None:
+                drain(*before)                                   # (the other slot: this chunk's kernels run meanwhile)
+            before = (slot, ev)
+        drain(*before)
+    return t_kernel, t_deflate, t_copy, t_write, written
+
+
 def text_bytes(F, param, store=None, unique_id=None, ranges=None):
     """(AGP, GFF) as PrintOutput writes them with ``param.outputs_on_gpu``, as bytes; with ``ranges`` (a list of (begin,
     end)) the bytes of those ranges of each file, in a list per file.  None: the layout is left to the host writer."""
@@ -923,12 +1044,17 @@ def PrintOutput(F, Information, output_dest, param, pass_nr, store=None, unique_
         pass
     print('(super)Contigs after scaffolding: ' + str(len(F)) + '\n', file=Information)
     t_start = time.time()
-    fasta = pass_dir + '/Scaffolds-pass' + str(pass_nr) + '.fa'
+    bgzf = bool(getattr(param, 'outputs_bgzf', False))
+    fasta = pass_dir + '/Scaffolds-pass' + str(pass_nr) + ('.fa.gz' if bgzf else '.fa')
     em = _Emitter(F, param, store, unique_id)
     try:
         partial = fasta + '.partial'
         try:
-            t_kernel, t_copy, t_write = _write_fasta_chunks(em, partial, CHUNK_BYTES)
+            if bgzf:
+                t_kernel, t_deflate, t_copy, t_write, file_bytes = _write_bgzf_chunks(em, partial, CHUNK_BYTES)
+            else:
+                t_kernel, t_copy, t_write = _write_fasta_chunks(em, partial, CHUNK_BYTES)
+                t_deflate, file_bytes = 0.0, em.total
             _report(em, param)
         except BaseException:
             if os.path.exists(partial):
@@ -958,7 +1084,8 @@ def PrintOutput(F, Information, output_dest, param, pass_nr, store=None, unique_
                 split = dict(text='host')
         last_timings.clear()
         last_timings.update(em.seconds, emit_kernels=t_kernel, d2h=t_copy, file_write=t_write,
-                            agp_gff=time.time() - t0, total=time.time() - t_start, fasta_bytes=em.total, **split)
+                            agp_gff=time.time() - t0, total=time.time() - t_start, fasta_bytes=em.total,
+                            bgzf_kernels=t_deflate, fasta_file_bytes=file_bytes, **split)
     finally:
         em.close()
     return ()

@@ -19,6 +19,7 @@ _PARAM_DEFAULTS = dict(
     contamination_ratio=0, contamination_mean=None, contamination_stddev=None,
     NO_ILP=None, FASTER_ILP=None,
     outputs_on_gpu=False,        # not the reference's: AGP / GFF text formatted on the device (GenerateOutput.PrintOutput)
+    outputs_bgzf=False,          # not the reference's: Scaffolds-pass<n>.fa.gz, BGZF-compressed on the device, instead of .fa
 )
 
 

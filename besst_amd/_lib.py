@@ -233,6 +233,11 @@ _SIGNATURES = {
     'besst_dev_text_emit': (C.c_int, [_P, C.POINTER(TextColumns), _P, C.c_size_t, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
     'besst_dev_wrap_fasta': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P,
                                        C.c_int64, C.c_int64, _P, _P]),
+    'besst_dev_bgzf_deflate_bound': (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    'besst_dev_bgzf_deflate_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int32]),
+    'besst_dev_bgzf_deflate': (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_size_t, _P, C.c_size_t, _P, _P]),
+    'besst_bgzf_deflate_device': (C.c_int, [C.c_int, _P, C.c_size_t, C.c_int32, C.c_int32, _P, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]),
 }
 
 _lib = None

@@ -11,7 +11,11 @@ writes ``pass<n>/Scaffolds-pass<n>.fa`` with its ``.agp`` and ``.gff`` (the sequ
 ``--outputs_on_gpu`` the AGP and GFF text is formatted on the GPU too, and ``repeats.fa`` / ``low_coverage_contigs.fa`` are
 written from the sequence store in one go where the contigs live there (``--fasta_on_gpu``).  ``--final_fasta`` leaves the
 directory as runBESST does without --separate_repeats: ``pass<n>/Scaffolds_pass<n>.fa`` holds the scaffolds followed by
-the repeats, ``Scaffolds-pass<n>.fa`` and, after the last pass, ``repeats.fa`` are gone.  BESST's path
+the repeats, ``Scaffolds-pass<n>.fa`` and, after the last pass, ``repeats.fa`` are gone.  With ``--bgzf_outputs`` the
+scaffold FASTA is compressed on the GPU and written as ``Scaffolds-pass<n>.fa.gz``, a BGZF file (what ``bgzip`` writes:
+``samtools faidx`` and every gzip reader open it), and no ``.fa``; ``--final_fasta`` then leaves
+``Scaffolds_pass<n>.fa.gz``, the repeats appended as further BGZF blocks.  AGP, GFF, ``repeats.fa``,
+``low_coverage_contigs.fa`` and the TSVs stay plain.  BESST's path
 search (PROWithinScaf / PROBetweenScaf) stays with BESST - see INTEGRATION.md for plugging these calls into runBESST.
 
 Several GPUs of one node: launch the same command line under torchrun, one process per GPU -
@@ -86,6 +90,9 @@ def build_parser():
                     help="leave runBESST's final files: pass<n>/Scaffolds_pass<n>.fa = the scaffolds followed by "
                          'repeats.fa (Scaffolds-pass<n>.fa is renamed, repeats.fa removed after the last pass); needs '
                          '--scaffolds')
+    ap.add_argument('--bgzf_outputs', dest='bgzf_outputs', action='store_true',
+                    help='write Scaffolds-pass<n>.fa.gz instead of .fa: BGZF (bgzip) blocks, compressed on the GPU from the '
+                         'buffer the FASTA is produced in (with --final_fasta: Scaffolds_pass<n>.fa.gz); needs --scaffolds')
     ap.add_argument('-filter_contigs', dest='contig_filter_length', type=int, default=None,
                     help='leave contigs shorter than this out of the run (runBESST -filter_contigs)')
     ap.add_argument('--threads', type=int, default=None, help='BAM inflate threads')
@@ -137,14 +144,36 @@ def write_scaffolds(G, G_prime, Contigs, small_contigs, Scaffolds, small_scaffol
           file=Information)
 
 
-def finish_pass_fasta(out, pass_nr):
+def finish_pass_fasta(out, pass_nr, bgzf=False):
     """runBESST:220-226: Scaffolds-pass<n>.fa becomes Scaffolds_pass<n>.fa, followed by repeats.fa as it stands now (the
-    scaffolds are renamed and the repeats appended: the large file is not copied)."""
+    scaffolds are renamed and the repeats appended: the large file is not copied).  ``bgzf``: the same for the pass's
+    .fa.gz - its EOF block is cut off, the repeats follow as BGZF blocks from the same compressor, then one EOF block."""
     pass_dir = os.path.join(out, 'pass%d' % pass_nr)
-    final = os.path.join(pass_dir, 'Scaffolds_pass%d.fa' % pass_nr)
-    os.replace(os.path.join(pass_dir, 'Scaffolds-pass%d.fa' % pass_nr), final)
+    ext = '.fa.gz' if bgzf else '.fa'
+    final = os.path.join(pass_dir, 'Scaffolds_pass%d%s' % (pass_nr, ext))
+    os.replace(os.path.join(pass_dir, 'Scaffolds-pass%d%s' % (pass_nr, ext)), final)
     repeats = os.path.join(out, 'repeats.fa')
-    if os.path.exists(repeats):
+    if bgzf:
+        eof = GO.BGZF_EOF
+        with open(final, 'r+b') as dst:
+            size = dst.seek(0, os.SEEK_END)
+            if size < len(eof):
+                raise IOError('%s does not end with the BGZF EOF block' % final)
+            dst.seek(size - len(eof))
+            if dst.read(len(eof)) != eof:
+                raise IOError('%s does not end with the BGZF EOF block' % final)
+            dst.truncate(size - len(eof))
+            dst.seek(size - len(eof))
+            if os.path.exists(repeats):
+                step = GO._bgzf_chunk(64 << 20)                  # whole blocks: only the file's last block is short
+                with open(repeats, 'rb') as src:
+                    while True:
+                        data = src.read(step)
+                        if not data:
+                            break
+                        dst.write(GO.bgzf_compress(data, eof=False))
+            dst.write(eof)
+    elif os.path.exists(repeats):
         with open(final, 'ab') as dst, open(repeats, 'rb') as src:
             shutil.copyfileobj(src, dst, 16 << 20)
     return final
@@ -184,6 +213,8 @@ def main(argv=None):
                  'scaffold step, and its path search, which would do the work instead, is not part of this package')
     if args.final_fasta and not args.scaffolds:
         sys.exit('--final_fasta needs --scaffolds: Scaffolds_pass<n>.fa is the scaffold FASTA followed by the repeats')
+    if args.bgzf_outputs and not args.scaffolds:
+        sys.exit('--bgzf_outputs needs --scaffolds: the file it compresses is the scaffold FASTA')
     if args.max_contig_overlap < 0 or args.max_contig_overlap > GO.MAX_CONTIG_OVERLAP_LIMIT:
         sys.exit('-max_contig_overlap must lie in 0..%d' % GO.MAX_CONTIG_OVERLAP_LIMIT)
     rank, joined = join_process_group()
@@ -211,6 +242,7 @@ def _run(args, rank):
     param.print_scores = False
     param.max_contig_overlap = args.max_contig_overlap
     param.outputs_on_gpu = args.outputs_on_gpu
+    param.outputs_bgzf = args.bgzf_outputs
     param.output_directory = out
     param.first_lib = True
     Information = param.information_file = open(os.path.join(out, 'Statistics.txt') if lead else os.devnull, 'w')
@@ -278,7 +310,7 @@ def _run(args, rank):
         if args.scaffolds:
             write_scaffolds(G, G_prime, Contigs, small_contigs, Scaffolds, small_scaffolds, Information, param, i + 1, store)
             if args.final_fasta:
-                finish_pass_fasta(out, i + 1)
+                finish_pass_fasta(out, i + 1, bgzf=args.bgzf_outputs)
         print('pass %d: %d records, G %d link edges, G_prime %d link edges' % (
             i + 1, len(records), sum(1 for u, v in G.edges() if G[u][v]['nr_links'] is not None),
             sum(1 for u, v in G_prime.edges() if G_prime[u][v]['nr_links'] is not None)))

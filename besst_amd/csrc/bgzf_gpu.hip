@@ -46,6 +46,7 @@
 #include <mutex>
 #include <string.h>
 
+#include "bgzf_crc.h"
 #include "common.h"
 
 namespace besst {
@@ -1150,27 +1151,9 @@ size_t bgzf_inflate_symbol_places(size_t inflated_bytes, size_t n_blocks) { retu
 // through - checks it, and so does this path: a damaged payload that still decodes, or a byte the window logic got wrong,
 // is a refused block, not a wrong record.  One workgroup per block, a thread per slice of <= 272 bytes: byte-table CRC
 // of the slice, then the slice's CRC is carried over the bytes behind it - multiplication by x^(8n) modulo the CRC polynomial,
-// zlib's crc32_combine, the powers from two tables - and the 256 values are XORed.
+// zlib's crc32_combine, the powers from two tables - and the 256 values are XORed.  (bgzf_crc.h: the tables and the
+// multiplication, shared with the compressor.)
 namespace {
-
-constexpr uint32_t kCrcPoly = 0xedb88320u;
-__device__ const uint32_t kCrcX2n[32] = {           // x^(2^k) mod the polynomial, reflected (zlib's x2n_table)
-    0x40000000u, 0x20000000u, 0x08000000u, 0x00800000u, 0x00008000u, 0xedb88320u, 0xb1e6b092u, 0xa06a2517u,
-    0xed627daeu, 0x88d14467u, 0xd7bbfe6au, 0xec447f11u, 0x8e7ea170u, 0x6427800eu, 0x4d47bae0u, 0x09fe548fu,
-    0x83852d0fu, 0x30362f1au, 0x7b5a9cc3u, 0x31fec169u, 0x9fec022au, 0x6c8dedc4u, 0x15d6874du, 0x5fde7a4eu,
-    0xbad90e37u, 0x2e4e5eefu, 0x4eaba214u, 0xa8a472c0u, 0x429a969eu, 0x148d302au, 0xc40ba6d0u, 0xc4e22c3cu};
-
-// a(x) * b(x) modulo the polynomial (both reflected: bit 31 is x^0), any operands per lane
-__device__ __forceinline__ uint32_t crc_mul_lanes(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-#pragma unroll 8
-    for (int j = 0; j < 32; ++j) {
-        p ^= (a & (1u << 31)) ? b : 0u;
-        a <<= 1;
-        b = (b & 1u) ? (b >> 1) ^ kCrcPoly : b >> 1;
-    }
-    return p;
-}
 
 // x^(8 n) modulo the polynomial for the n a slice's CRC has to be carried over: kCrcPow16[j] = x^(128 j) (whole slices behind
 // it: slices are multiples of 16 bytes), kCrcPow8[r] = x^(8 r) (the last slice's bytes).  Filled once per device by
@@ -1203,18 +1186,7 @@ __global__ __launch_bounds__(256) void bgzf_crc_kernel(const uint8_t* __restrict
     if (b >= n_blocks) return;
     const uint32_t len = blocks[b].dst_len;
     if (len == 0u || status[b] != kInfOk) return;            // uniform
-    {   // the byte table: entry t is t carried through eight steps of the polynomial division
-        uint32_t c = t;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ kCrcPoly : c >> 1;
-        s_tab[0][t] = c;
-        __syncthreads();
-#pragma unroll
-        for (int j = 1; j < 4; ++j) {
-            c = s_tab[0][c & 0xffu] ^ (c >> 8);
-            s_tab[j][t] = c;
-        }
-    }
+    crc_fill_tables(s_tab, t);
     __syncthreads();
     const uint8_t* first = inflated + (size_t)blocks[b].dst_off_lo + ((size_t)blocks[b].dst_off_hi << 32);
     // The blocks of a chunk lie back to back (a record may run on into the next block), so a block begins at any byte: the
@@ -1234,14 +1206,13 @@ __global__ __launch_bounds__(256) void bgzf_crc_kernel(const uint8_t* __restrict
     uint32_t crc = 0xffffffffu;
     auto eat = [&](uint32_t w, uint32_t from, uint32_t count) {   // bytes [from, count) of a word
         if (from == 0u && count >= 4u) {
-            const uint32_t x = crc ^ w;
-            crc = s_tab[3][x & 0xffu] ^ s_tab[2][(x >> 8) & 0xffu] ^ s_tab[1][(x >> 16) & 0xffu] ^ s_tab[0][x >> 24];
+            crc = crc_dword(s_tab, crc, w);
             return;
         }
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k) {
             if (k >= from && k < count) {
-                crc = s_tab[0][(crc ^ (w >> (8u * k))) & 0xffu] ^ (crc >> 8);
+                crc = crc_byte(s_tab, crc, w >> (8u * k));
             }
         }
     };

@@ -39,7 +39,8 @@ extern "C" {
  * built against 2 passes a shorter struct: recompile), + besst_dev_mate_bits.  Added since without a new version
  * (additions only): the scaffold-output entry points besst_{dev,host}_seq_overlaps / besst_{dev,host}_emit_scaffolds; the
  * FASTA reader besst_dev_fasta_workspace_bytes / besst_dev_fasta_scan / besst_dev_fasta_pack; the text of the output stage
- * besst_dev_text_workspace_bytes / besst_dev_text_measure / besst_dev_text_emit / besst_dev_wrap_fasta. */
+ * besst_dev_text_workspace_bytes / besst_dev_text_measure / besst_dev_text_emit / besst_dev_wrap_fasta,
+ * besst_dev_bgzf_deflate_bound / besst_dev_bgzf_deflate_workspace_bytes / besst_dev_bgzf_deflate / besst_bgzf_deflate_device. */
 #define BESST_ABI_VERSION 3
 
 /* status codes */
@@ -855,6 +856,33 @@ int besst_dev_wrap_fasta(void* stream, const uint8_t* pool, int64_t pool_bytes, 
                          const int32_t* ctg_len, const uint8_t* names, int64_t names_bytes, const int64_t* name_off,
                          int64_t n_rows, const int64_t* rows, const int64_t* rec_off, int64_t begin, int64_t end,
                          uint8_t* out, uint64_t* err);
+
+/* ---- BGZF compression of device bytes (csrc/bgzf_deflate.hip; GenerateOutput.py: param.outputs_bgzf) -------------------
+ * n_bytes of device memory become a BGZF file: blocks of block_payload input bytes (1..BESST_BGZF_BLOCK_PAYLOAD; only the
+ * last may be shorter; none for n_bytes = 0), each an 18-byte header (1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00,
+ * BSIZE - 1), ONE final DEFLATE block, CRC-32 and ISIZE.  The DEFLATE block is dynamic Huffman over literals and matches
+ * of distance 1 that never reach in front of the block - or stored, where that would not be smaller than payload + 5
+ * bytes: a block is at most payload + 31 bytes.  with_eof appends the 28-byte EOF block.  The same input gives the same
+ * bytes.
+ *   besst_dev_bgzf_deflate_bound            n_bytes + 31 * ceil(n_bytes / block_payload) (+ 28): what `out` must hold
+ *                                           (0: block_payload out of range).  Needs no GPU.
+ *   besst_dev_bgzf_deflate_workspace_bytes  scratch of one call: a slot of 64 KiB per block, sizes and offsets (0 as above)
+ *   besst_dev_bgzf_deflate                  three kernels on `stream`; out_bytes (device): the file's length; block_off
+ *                                           (device, n_blocks + 1 entries, or null): where every block begins, and the end of
+ *                                           the last.  BESST_ERR_ARG without touching the device: a null pointer, a
+ *                                           block_payload out of range, a workspace or output smaller than the two sizes.
+ *                                           The kernels read src in aligned 4-byte words: up to 3 bytes in front of a src
+ *                                           that is no multiple of four and up to 3 behind src + n_bytes are read (never
+ *                                           across a page) and not used.
+ *   besst_bgzf_deflate_device               host buffers in and out (the counterpart of besst_bgzf_inflate_device) */
+#define BESST_BGZF_BLOCK_PAYLOAD 65280
+size_t besst_dev_bgzf_deflate_bound(int64_t n_bytes, int32_t block_payload, int32_t with_eof);
+size_t besst_dev_bgzf_deflate_workspace_bytes(int64_t n_bytes, int32_t block_payload);
+int besst_dev_bgzf_deflate(void* stream, const void* src, int64_t n_bytes, int32_t block_payload, int32_t with_eof,
+                           void* workspace, size_t workspace_bytes, void* out, size_t out_cap, int64_t* out_bytes,
+                           int64_t* block_off);
+int besst_bgzf_deflate_device(int device, const void* src, size_t n_bytes, int32_t block_payload, int32_t with_eof, void* out,
+                              size_t out_cap, size_t* out_len);
 
 #ifdef __cplusplus
 }
