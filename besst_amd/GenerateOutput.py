@@ -7,12 +7,16 @@ they DELETE the removed contigs from the caller's dicts.
 ``info-pass<n>.gff``.  The sequence work is done on the device (csrc/emit.hip): the contigs lie in a
 :class:`SequenceStore` in HBM for the whole run, ``seq_overlap_kernel`` finds the overlaps of the junctions that may
 merge, the host turns placements + overlaps into a piece table with numpy, and ``emit_kernel`` gathers the FASTA bytes
-(copy / reverse-complement / 'N' fill) in chunks that are copied back and written while the next chunk is produced.
-With ``param.outputs_bgzf`` the chunks are compressed on the device first (csrc/bgzf_deflate.hip) and the file is
+(copy / reverse-complement / 'N' fill).
+With ``param.outputs_bgzf`` the bytes are compressed on the device first (csrc/bgzf_deflate.hip) and the file is
 ``Scaffolds-pass<n>.fa.gz``, a BGZF file: only the compressed bytes cross PCIe.
 AGP and GFF are plain text from names, positions and gaps: on the host by default, and with ``param.outputs_on_gpu`` formatted
 on the device from flat columns and the store's name pool (csrc/emit_text.hip).  A store with ``batch_fasta`` set also
 writes ``repeats.fa`` / ``low_coverage_contigs.fa`` from the pool with one kernel instead of one fetch per contig.
+Every file that is produced on the device is a byte source (``total`` bytes, ``emit`` of a range, ``check`` after the last
+range: :class:`ScaffoldEmitter`, ``_TextEmitter.file``, ``wrapped_fasta_source``) and reaches the host through one
+pipeline, :func:`write_chunks`: chunks cut by :func:`chunk_plan` go through two slots of device and pinned buffers, the
+copy and the file write of chunk c running while the kernels of chunk c + 1 do.
 ``SequenceStore.from_fasta`` fills the store from the contig
 FASTA itself (csrc/fasta.hip: the file's bytes are parsed in HBM by the rules of runBESST:45-74); ``C_dict`` then holds
 :class:`SequenceRef` handles instead of strings.  Like the rest of the package there is no CPU path: without
@@ -21,6 +25,7 @@ the library or a GPU these calls raise :class:`besst_amd._lib.BesstDeviceError`.
 from __future__ import print_function
 
 import ctypes as _C
+import io
 import os
 import time
 import warnings
@@ -68,19 +73,22 @@ def _write_from_pool(cont_objs, path):
     return True
 
 
-def PrintOutRepeats(Repeats, Contigs, output_dest, small_contigs):
-    if output_dest and _write_from_pool(Repeats, output_dest + '/repeats.fa'):
-        for cont_obj in Repeats:
-            _forget(cont_obj, Contigs, small_contigs)
-        return ()
-    handle = open(output_dest + '/repeats.fa', 'w') if output_dest else None
-    for cont_obj in Repeats:
+def _print_out_fasta(cont_objs, Contigs, output_dest, small_contigs, file_name):
+    """reference :47-53, 68-74: the contigs as wrapped FASTA into ``file_name`` (no ``output_dest``: no file), every one
+    of them deleted from the caller's dicts."""
+    path = output_dest + '/' + file_name if output_dest else None
+    handle = open(path, 'w') if path and not _write_from_pool(cont_objs, path) else None
+    for cont_obj in cont_objs:
         if handle:
             _write_fasta(handle, cont_obj.name, cont_obj.sequence)
         _forget(cont_obj, Contigs, small_contigs)
     if handle:
         handle.close()
     return ()
+
+
+def PrintOutRepeats(Repeats, Contigs, output_dest, small_contigs):
+    return _print_out_fasta(Repeats, Contigs, output_dest, small_contigs, 'repeats.fa')
 
 
 def repeat_contigs_logger(Repeats, Contigs, output_dest, small_contigs, param):
@@ -98,18 +106,7 @@ def repeat_contigs_logger(Repeats, Contigs, output_dest, small_contigs, param):
 
 
 def PrintOut_low_cowerage_contigs(low_coverage_contigs, Contigs, output_dest, small_contigs):
-    if output_dest and _write_from_pool(low_coverage_contigs, output_dest + '/low_coverage_contigs.fa'):
-        for cont_obj in low_coverage_contigs:
-            _forget(cont_obj, Contigs, small_contigs)
-        return ()
-    handle = open(output_dest + '/low_coverage_contigs.fa', 'w') if output_dest else None
-    for cont_obj in low_coverage_contigs:
-        if handle:
-            _write_fasta(handle, cont_obj.name, cont_obj.sequence)
-        _forget(cont_obj, Contigs, small_contigs)
-    if handle:
-        handle.close()
-    return ()
+    return _print_out_fasta(low_coverage_contigs, Contigs, output_dest, small_contigs, 'low_coverage_contigs.fa')
 
 
 def ChangeToSmallContigs(Contigs, list_of_contigs, small_contigs):
@@ -577,11 +574,28 @@ class ScaffoldLayout(object):
         return c, int(self.off[c] + self.len[c] - 1 - pos)      # reversed: oriented position pos is that far from the end
 
 
-class _Emitter(object):
-    """A layout on the device: overlaps computed, piece table uploaded, ranges of the FASTA on request."""
+def _out_buffer(torch, dev, n, pad=0):
+    """A uint8 device tensor that takes ``n`` produced bytes: whole 16-byte groups (the kernels store those), one at least,
+    and ``pad`` readable bytes behind them."""
+    return torch.empty(max(16, (n + 15) // 16 * 16) + pad, dtype=torch.uint8, device=dev)
+
+
+class ByteSource(object):
+    """A file that is produced on the device, as write_chunks and source_bytes take it: ``total`` bytes on ``dev``;
+    ``emit(begin, end, out, stream)`` enqueues bytes [begin, end) into the uint8 device tensor ``out`` (16-byte aligned)
+    and waits for nothing; ``check()``, once after the last range has been consumed, synchronises and raises what went
+    wrong in any of them."""
+
+    def __init__(self, torch, dev, total, emit, check):
+        self.torch, self.dev, self.total, self.emit, self.check = torch, dev, total, emit, check
+
+
+class ScaffoldEmitter(object):
+    """A layout on the device: overlaps computed, piece table uploaded; the byte source of the scaffold FASTA."""
 
     def __init__(self, F, param, store, unique_id, device=0):
         t0 = time.time()
+        self.param = param
         if unique_id is None:
             unique_id = int(time.time())
         self.own_store = store is None
@@ -645,103 +659,25 @@ class _Emitter(object):
             p(self._len.data_ptr()), p(self._mode.data_ptr()), p(self._out_off.data_ptr()), int(begin), int(end),
             p(out.data_ptr()), p(self._err.data_ptr() + 16)), 'besst_dev_emit_scaffolds')
 
-    def key_error(self):
-        """After the last range: None, or (flat contig index, KeyError to raise) like the reference's first failure."""
+    def check(self):
+        """After the last range: the `merging` lines the reference prints up to its first KeyError go to
+        ``param.information_file``, then that error is raised."""
         self.torch.cuda.synchronize(self.dev)
         err = self._err.cpu().numpy().view(np.uint64)
         if int(err[3]) != NO_ERROR:
             raise BesstDeviceError('besst_dev_emit_scaffolds: piece %d points outside its pool' % int(err[3]))
         hit = self.layout.locate(int(err[2]), int(err[0]))
-        if hit is None:
-            return None
-        return hit[0], KeyError(chr(self.store.byte_at(hit[1])))
-
-    def merging_lines(self, before=None):
-        return ['merging {0} bp here'.format(n) for c, n in self.table['merges'] if before is None or c < before]
+        error = None if hit is None else KeyError(chr(self.store.byte_at(hit[1])))
+        for c, n in self.table['merges']:
+            if hit is None or c < hit[0]:
+                print('merging {0} bp here'.format(n), file=self.param.information_file)
+        if error is not None:
+            raise error
 
     def close(self):
         if self.own_store:
             self.store.close()
         self._lit = self._src = self._len = self._mode = self._out_off = self._err = None
-
-
-def _report(em, param):
-    """The `merging` lines the reference prints up to its first KeyError, then that error."""
-    bad = em.key_error()
-    for line in em.merging_lines(None if bad is None else bad[0]):
-        print(line, file=param.information_file)
-    if bad is not None:
-        raise bad[1]
-
-
-def scaffold_bytes(F, param, store=None, unique_id=None, chunk_bytes=None, bgzf=False):
-    """The FASTA text PrintOutput would write, as bytes (``chunk_bytes``: produced in ranges of that many bytes).  ``bgzf``:
-    the BGZF file PrintOutput writes with ``param.outputs_bgzf`` instead (ranges of whole blocks within ``chunk_bytes``)."""
-    em = _Emitter(F, param, store, unique_id)
-    try:
-        torch, total = em.torch, em.total
-        step = total if not chunk_bytes else int(chunk_bytes)
-        if bgzf:
-            step = _bgzf_chunk(step)
-        parts = []
-        with torch.cuda.device(em.dev):
-            buf = torch.empty(max(16, (min(step, total) + 15) // 16 * 16) + (EMIT_PAD if bgzf else 0), dtype=torch.uint8,
-                              device=em.dev)            # (the compressor reads whole words: up to 3 bytes behind its input)
-            press = _Deflater(torch, em.dev, min(step, total)) if bgzf else None
-            for begin in (range(0, total, max(step, 1)) if total or not bgzf else [0]):
-                end = min(total, begin + step)
-                if end > begin:
-                    em.emit(begin, end, buf)
-                if bgzf:
-                    press.run(buf, end - begin, end == total)
-                    parts.append(press.out[:int(press.length.item())].cpu().numpy().tobytes())
-                else:
-                    parts.append(buf[:end - begin].cpu().numpy().tobytes())
-        _report(em, param)
-        return b''.join(parts)
-    finally:
-        em.close()
-
-
-def _write_fasta_chunks(em, path, chunk_bytes):
-    """emit_kernel -> device buffer -> pinned buffer -> file, two of each: the copy and the write of chunk c run while the
-    kernel of chunk c + 1 does.  -> seconds spent in (kernels, copies, file writes)."""
-    torch, dev, total = em.torch, em.dev, em.total
-    size = max(16, (min(chunk_bytes, total) + 15) // 16 * 16)
-    t_kernel = t_copy = t_write = 0.0
-    with torch.cuda.device(dev), open(path, 'wb') as fh:
-        d_buf = [torch.empty(size, dtype=torch.uint8, device=dev) for _ in range(2)]
-        h_buf = [torch.empty(size, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        compute, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
-        pending = []                                             # (slot, bytes, events) of chunks not yet written
-
-        def drain():
-            nonlocal t_kernel, t_copy, t_write
-            slot, n, (k0, k1, c0, c1) = pending.pop(0)
-            c1.synchronize()
-            t_kernel += k0.elapsed_time(k1) * 1e-3
-            t_copy += c0.elapsed_time(c1) * 1e-3
-            t0 = time.time()
-            fh.write(memoryview(h_buf[slot].numpy())[:n])
-            t_write += time.time() - t0
-
-        for i, begin in enumerate(range(0, total, size)):
-            end, slot = min(total, begin + size), i % 2
-            if len(pending) == 2:
-                drain()                                          # frees this slot's two buffers
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-            ev[0].record(compute)
-            em.emit(begin, end, d_buf[slot], compute)
-            ev[1].record(compute)
-            copy.wait_event(ev[1])
-            with torch.cuda.stream(copy):
-                ev[2].record(copy)
-                h_buf[slot][:end - begin].copy_(d_buf[slot][:end - begin], non_blocking=True)
-                ev[3].record(copy)
-            pending.append((slot, end - begin, ev))
-        while pending:
-            drain()
-    return t_kernel, t_copy, t_write
 
 
 class _TextEmitter(object):
@@ -805,9 +741,11 @@ class _TextEmitter(object):
                                                 p(self._info.data_ptr())), 'besst_dev_text_emit')
 
     def file(self, which):
-        return _ByteSource(self.torch, self.dev, self.totals[which], lambda b, e, out, stream: self.emit(which, b, e, out, stream))
+        """The AGP or GFF file as a byte source."""
+        return ByteSource(self.torch, self.dev, self.totals[which],
+                          lambda begin, end, out, stream: self.emit(which, begin, end, out, stream), self.check)
 
-    def finish(self):
+    def check(self):
         self.torch.cuda.synchronize(self.dev)
         self._check(int(self._info.cpu().numpy().view(np.uint64)[2]))
 
@@ -815,21 +753,14 @@ class _TextEmitter(object):
         self._keep = self._ws = self._info = self.cols = None
 
 
-class _ByteSource(object):
-    """What _write_fasta_chunks asks of a file that is produced on the device: its size and byte ranges of it."""
-
-    def __init__(self, torch, dev, total, emit):
-        self.torch, self.dev, self.total, self.emit = torch, dev, total, emit
-
-
-def _bgzf_chunk(chunk_bytes):
+def bgzf_chunk(chunk_bytes):
     """The largest multiple of the block payload within ``chunk_bytes`` (one block at least): chunks cut there leave every
     block of a file but its last full."""
     payload = int(BGZF_BLOCK_PAYLOAD)
     return max(1, int(chunk_bytes) // payload) * payload
 
 
-class _Deflater(object):
+class Deflater(object):
     """Device buffers of one BGZF compression of up to ``cap`` bytes (csrc/bgzf_deflate.hip): workspace, output, length."""
 
     def __init__(self, torch, dev, cap):
@@ -873,90 +804,138 @@ def bgzf_compress(data, block_payload=None, eof=True, device=0):
     return out[:n.value].tobytes()
 
 
-def _write_bgzf_chunks(src, path, chunk_bytes, eof=True):
-    """The compressed sibling of _write_fasta_chunks: emit -> device buffer -> BGZF blocks on the device -> pinned buffer ->
-    file, two of each.  A chunk is a whole number of blocks; the kernels of chunk c + 1 are enqueued before the length of
-    chunk c is waited for, and only the compressed bytes are copied back.
-    -> seconds spent in (emit kernels, deflate kernels, copies, file writes), bytes written"""
-    torch, dev, total = src.torch, src.dev, src.total
-    chunk = _bgzf_chunk(chunk_bytes)
-    size = min(chunk, max(total, 1))
-    t_kernel = t_deflate = t_copy = t_write = 0.0
-    written = 0
-    with torch.cuda.device(dev), open(path, 'wb') as fh:
-        d_buf = [torch.empty((size + 15) // 16 * 16 + EMIT_PAD, dtype=torch.uint8, device=dev) for _ in range(2)]
-        press = [_Deflater(torch, dev, size) for _ in range(2)]
-        h_buf = [torch.empty(press[0].bound, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        h_len = [torch.zeros(1, dtype=torch.int64).pin_memory() for _ in range(2)]
+def chunk_plan(total, chunk_bytes, deflate):
+    """How a file of ``total`` bytes is cut into chunks -> [(begin, end, is_last)].  Plain: at every ``chunk_bytes``.
+    Deflated: at every bgzf_chunk(chunk_bytes), whole blocks, so that only the file's last block is short; an empty file is
+    one empty chunk, the one that carries the EOF block."""
+    step = bgzf_chunk(chunk_bytes) if deflate else max(1, int(chunk_bytes))
+    if deflate and not total:
+        return [(0, 0, True)]
+    return [(begin, min(total, begin + step), begin + step >= total) for begin in range(0, total, step)]
+
+
+def write_chunks(src, fh, chunk_bytes, deflate=False):
+    """The one way of a byte source to the host: emit -> device buffer (``deflate``: -> BGZF blocks on the device,
+    csrc/bgzf_deflate.hip) -> pinned buffer -> ``fh``, a binary file object, then ``src.check()``.  Two slots of every
+    buffer: the kernels of chunk c + 1 are enqueued before the host waits for anything of chunk c, whose copy and file
+    write run meanwhile.  Plain, the copy is enqueued right behind the kernel; deflated, the chunk's length comes back
+    first and then only that many bytes.
+    -> dict(emit_kernels, bgzf_kernels, d2h, file_write: seconds; file_bytes: bytes written)"""
+    torch, dev = src.torch, src.dev
+    plan = chunk_plan(src.total, chunk_bytes, deflate)
+    spent = dict(emit_kernels=0.0, bgzf_kernels=0.0, d2h=0.0, file_write=0.0, file_bytes=0)
+    with torch.cuda.device(dev):
+        cap = max([1] + [end - begin for begin, end, _last in plan])
+        slots = range(min(2, len(plan)))
+        # (the compressor reads whole words: up to 3 bytes behind its input)
+        d_buf = [_out_buffer(torch, dev, cap, EMIT_PAD if deflate else 0) for _ in slots]
+        press = [Deflater(torch, dev, cap) for _ in slots] if deflate else None
+        h_buf = [torch.empty(press[0].bound if deflate else cap, dtype=torch.uint8).pin_memory() for _ in slots]
+        h_len = [torch.zeros(1, dtype=torch.int64).pin_memory() for _ in slots] if deflate else None
         compute, copy = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+        timed = lambda: torch.cuda.Event(enable_timing=True)
 
-        def drain(slot, ev):
-            nonlocal t_kernel, t_deflate, t_copy, t_write, written
-            ev[3].synchronize()                                  # the chunk's length is on the host
-            n = int(h_len[slot][0])
-            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        def copy_back(slot, n, source):
             with torch.cuda.stream(copy):
+                c0, c1 = timed(), timed()
                 c0.record(copy)
-                h_buf[slot][:n].copy_(press[slot].out[:n], non_blocking=True)
+                h_buf[slot][:n].copy_(source[:n], non_blocking=True)
                 c1.record(copy)
-            c1.synchronize()
-            t_kernel += ev[0].elapsed_time(ev[1]) * 1e-3
-            t_deflate += ev[1].elapsed_time(ev[2]) * 1e-3
-            t_copy += c0.elapsed_time(c1) * 1e-3
-            t0 = time.time()
-            fh.write(memoryview(h_buf[slot].numpy())[:n])
-            t_write += time.time() - t0
-            written += n
+            return c0, c1
 
-        before = None
-        for i, begin in enumerate(range(0, total, chunk) if total else [0]):
-            end, slot = min(total, begin + chunk), i % 2
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] + [torch.cuda.Event()]
-            ev[0].record(compute)
+        def enqueue(slot, begin, end, last):
+            k0, k1 = timed(), timed()
+            k0.record(compute)
             if end > begin:
                 src.emit(begin, end, d_buf[slot], compute)
-            ev[1].record(compute)
-            press[slot].run(d_buf[slot], end - begin, eof and end == total, compute)
-            ev[2].record(compute)
-            copy.wait_event(ev[2])
+            k1.record(compute)
+            if not deflate:
+                copy.wait_event(k1)
+                return slot, end - begin, k0, k1, None, copy_back(slot, end - begin, d_buf[slot])
+            press[slot].run(d_buf[slot], end - begin, last, compute)
+            k2 = timed()
+            k2.record(compute)
+            copy.wait_event(k2)
             with torch.cuda.stream(copy):
                 h_len[slot].copy_(press[slot].length, non_blocking=True)
-                ev[3].record(copy)
+                ready = torch.cuda.Event()
+                ready.record(copy)
+            return slot, None, k0, k1, k2, ready
+
+        def drain(slot, n, k0, k1, k2, copied):
+            if deflate:
+                copied.synchronize()                             # the chunk's length is on the host
+                n = int(h_len[slot][0])
+                copied = copy_back(slot, n, press[slot].out)
+                spent['bgzf_kernels'] += k1.elapsed_time(k2) * 1e-3
+            copied[1].synchronize()                              # frees this slot's buffers
+            spent['emit_kernels'] += k0.elapsed_time(k1) * 1e-3
+            spent['d2h'] += copied[0].elapsed_time(copied[1]) * 1e-3
+            t0 = time.time()
+            fh.write(memoryview(h_buf[slot].numpy())[:n])
+            spent['file_write'] += time.time() - t0
+            spent['file_bytes'] += n
+
+        before = None
+        for i, (begin, end, last) in enumerate(plan):
+            chunk = enqueue(i % 2, begin, end, last)
             if before is not None:
                 drain(*before)                                   # (the other slot: this chunk's kernels run meanwhile)
-            before = (slot, ev)
-        drain(*before)
-    return t_kernel, t_deflate, t_copy, t_write, written
+            before = chunk
+        if before is not None:
+            drain(*before)
+    src.check()
+    return spent
+
+
+def write_file(src, path, chunk_bytes, deflate=False):
+    """write_chunks into a new file at ``path`` -> its dict."""
+    with open(path, 'wb') as fh:
+        return write_chunks(src, fh, chunk_bytes, deflate)
+
+
+def source_bytes(src, ranges=None):
+    """The file of a byte source as bytes; ``ranges`` (a list of (begin, end)) -> a list of those ranges' bytes."""
+    torch, got = src.torch, []
+    with torch.cuda.device(src.dev):
+        for begin, end in ([(0, src.total)] if ranges is None else ranges):
+            buf = _out_buffer(torch, src.dev, end - begin)
+            src.emit(begin, end, buf, torch.cuda.current_stream(src.dev))
+            got.append(buf[:end - begin].cpu().numpy().tobytes())
+    src.check()
+    return got[0] if ranges is None else got
+
+
+def scaffold_bytes(F, param, store=None, unique_id=None, chunk_bytes=None, bgzf=False):
+    """The FASTA text PrintOutput would write, as bytes (``chunk_bytes``: produced in ranges of that many bytes).  ``bgzf``:
+    the BGZF file PrintOutput writes with ``param.outputs_bgzf`` instead (ranges of whole blocks within ``chunk_bytes``)."""
+    em = ScaffoldEmitter(F, param, store, unique_id)
+    try:
+        out = io.BytesIO()
+        write_chunks(em, out, chunk_bytes or em.total, bgzf)
+        return out.getvalue()
+    finally:
+        em.close()
 
 
 def text_bytes(F, param, store=None, unique_id=None, ranges=None):
     """(AGP, GFF) as PrintOutput writes them with ``param.outputs_on_gpu``, as bytes; with ``ranges`` (a list of (begin,
     end)) the bytes of those ranges of each file, in a list per file.  None: the layout is left to the host writer."""
-    em = _Emitter(F, param, store, unique_id)
+    em = ScaffoldEmitter(F, param, store, unique_id)
     try:
         text = _TextEmitter.make(em)
         if text is None:
             return None
-        torch = em.torch
-        out = []
-        with torch.cuda.device(em.dev):
-            for which in (TEXT_AGP, TEXT_GFF):
-                total, got = text.totals[which], []
-                for begin, end in ([(0, total)] if ranges is None else ranges):
-                    buf = torch.empty(max(16, (end - begin + 15) // 16 * 16), dtype=torch.uint8, device=em.dev)
-                    text.emit(which, begin, end, buf)
-                    got.append(buf[:end - begin].cpu().numpy().tobytes())
-                out.append(got[0] if ranges is None else got)
-        text.finish()
+        out = tuple(source_bytes(text.file(which), ranges) for which in (TEXT_AGP, TEXT_GFF))
         text.close()
-        return tuple(out)
+        return out
     finally:
         em.close()
 
 
 def wrapped_fasta_source(store, rows):
-    """The wrapped FASTA ('>' name, lines of FASTA_LINE bases) of the store's ``rows``, in that order, as a device byte
-    source -> (_ByteSource, check): ``check()`` after the last range raises if a record did not fit its table."""
+    """The wrapped FASTA ('>' name, lines of FASTA_LINE bases) of the store's ``rows``, in that order, as a byte source;
+    its ``check()`` raises if a record did not fit its table."""
     torch, dev = _torch_device(store.device.index)
     lib = _lib.load()
     names, name_off, name_at = store.name_pool()
@@ -971,9 +950,7 @@ def wrapped_fasta_source(store, rows):
     err = torch.full((1,), -1, dtype=torch.int64, device=dev)
     p = _C.c_void_p
 
-    def emit(begin, end, out, stream=None):
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
+    def emit(begin, end, out, stream):
         _lib.check(lib.besst_dev_wrap_fasta(
             p(stream.cuda_stream), p(store.pool_ptr), store.pool_bytes, len(store), p(store._off.data_ptr()),
             p(store._len.data_ptr()), p(names.data_ptr()), int(name_at[-1]), p(name_off.data_ptr()), len(rows),
@@ -985,29 +962,18 @@ def wrapped_fasta_source(store, rows):
         if bad != NO_ERROR:
             raise BesstDeviceError('besst_dev_wrap_fasta: record %d does not fit its table' % bad)
 
-    return _ByteSource(torch, dev, int(rec_off[-1]), emit), check
+    return ByteSource(torch, dev, int(rec_off[-1]), emit, check)
 
 
 def wrapped_fasta_bytes(store, rows, ranges=None):
     """The wrapped FASTA of ``rows`` as bytes (``ranges``: a list of (begin, end) -> a list of those ranges' bytes)."""
-    src, check = wrapped_fasta_source(store, rows)
-    torch, got = src.torch, []
-    with torch.cuda.device(src.dev):
-        for begin, end in ([(0, src.total)] if ranges is None else ranges):
-            buf = torch.empty(max(16, (end - begin + 15) // 16 * 16), dtype=torch.uint8, device=src.dev)
-            src.emit(begin, end, buf)
-            got.append(buf[:end - begin].cpu().numpy().tobytes())
-    check()
-    return got[0] if ranges is None else got
+    return source_bytes(wrapped_fasta_source(store, rows), ranges)
 
 
 def write_wrapped_fasta(store, rows, path):
     """``rows`` of the store as wrapped FASTA to ``path``: no contig passes through a Python string.
-    -> seconds spent in (kernels, copies, file writes)"""
-    src, check = wrapped_fasta_source(store, rows)
-    seconds = _write_fasta_chunks(src, path, CHUNK_BYTES)
-    check()
-    return seconds
+    -> write_chunks' dict"""
+    return write_file(wrapped_fasta_source(store, rows), path, CHUNK_BYTES)
 
 
 def _write_agp_gff(layout, agp, gff):
@@ -1046,16 +1012,11 @@ def PrintOutput(F, Information, output_dest, param, pass_nr, store=None, unique_
     t_start = time.time()
     bgzf = bool(getattr(param, 'outputs_bgzf', False))
     fasta = pass_dir + '/Scaffolds-pass' + str(pass_nr) + ('.fa.gz' if bgzf else '.fa')
-    em = _Emitter(F, param, store, unique_id)
+    em = ScaffoldEmitter(F, param, store, unique_id)
     try:
         partial = fasta + '.partial'
         try:
-            if bgzf:
-                t_kernel, t_deflate, t_copy, t_write, file_bytes = _write_bgzf_chunks(em, partial, CHUNK_BYTES)
-            else:
-                t_kernel, t_copy, t_write = _write_fasta_chunks(em, partial, CHUNK_BYTES)
-                t_deflate, file_bytes = 0.0, em.total
-            _report(em, param)
+            spent = write_file(em, partial, CHUNK_BYTES, bgzf)
         except BaseException:
             if os.path.exists(partial):
                 os.remove(partial)
@@ -1065,14 +1026,13 @@ def PrintOutput(F, Information, output_dest, param, pass_nr, store=None, unique_
         text = _TextEmitter.make(em) if getattr(param, 'outputs_on_gpu', False) else None
         split = {}
         if text is not None:
-            # binary files from the device buffers, through the pinned double buffer of the FASTA
+            # binary files from the device buffers, through the pipeline of the FASTA
             try:
-                spent = [_write_fasta_chunks(text.file(which), pass_dir + '/info-pass' + str(pass_nr) + ext, CHUNK_BYTES)
+                files = [write_file(text.file(which), pass_dir + '/info-pass' + str(pass_nr) + ext, CHUNK_BYTES)
                          for which, ext in ((TEXT_GFF, '.gff'), (TEXT_AGP, '.agp'))]
-                text.finish()
                 split = dict(text='device', text_prep=text.prep_seconds,
-                             text_kernels=text.measure_seconds + spent[0][0] + spent[1][0],
-                             text_d2h=spent[0][1] + spent[1][1], text_write=spent[0][2] + spent[1][2],
+                             text_kernels=text.measure_seconds + sum(f['emit_kernels'] for f in files),
+                             text_d2h=sum(f['d2h'] for f in files), text_write=sum(f['file_write'] for f in files),
                              text_bytes=sum(text.totals))
             finally:
                 text.close()
@@ -1083,9 +1043,9 @@ def PrintOutput(F, Information, output_dest, param, pass_nr, store=None, unique_
             if getattr(param, 'outputs_on_gpu', False):
                 split = dict(text='host')
         last_timings.clear()
-        last_timings.update(em.seconds, emit_kernels=t_kernel, d2h=t_copy, file_write=t_write,
-                            agp_gff=time.time() - t0, total=time.time() - t_start, fasta_bytes=em.total,
-                            bgzf_kernels=t_deflate, fasta_file_bytes=file_bytes, **split)
+        last_timings.update(em.seconds, emit_kernels=spent['emit_kernels'], bgzf_kernels=spent['bgzf_kernels'],
+                            d2h=spent['d2h'], file_write=spent['file_write'], fasta_file_bytes=spent['file_bytes'],
+                            agp_gff=time.time() - t0, total=time.time() - t_start, fasta_bytes=em.total, **split)
     finally:
         em.close()
     return ()

@@ -165,7 +165,7 @@ def finish_pass_fasta(out, pass_nr, bgzf=False):
             dst.truncate(size - len(eof))
             dst.seek(size - len(eof))
             if os.path.exists(repeats):
-                step = GO._bgzf_chunk(64 << 20)                  # whole blocks: only the file's last block is short
+                step = GO.bgzf_chunk(64 << 20)                  # whole blocks: only the file's last block is short
                 with open(repeats, 'rb') as src:
                     while True:
                         data = src.read(step)

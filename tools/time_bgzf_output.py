@@ -76,13 +76,13 @@ def main():
         doc['bgzf_wall_below_plain_wall'] = bool(doc['bgzf']['wall_s']['median'] < doc['plain']['wall_s']['median'])
         doc['verified_vs_plain_file'] = True
         # the three kernels of one chunk next to a device-to-device copy of its payload
-        n = min(len(plain), GO._bgzf_chunk(GO.CHUNK_BYTES))
+        n = min(len(plain), GO.bgzf_chunk(GO.CHUNK_BYTES))
         with torch.cuda.device(dev):
             src = torch.from_numpy(np.frombuffer(plain[:n], dtype=np.uint8).copy()).to(dev)
             pad = torch.zeros(n + GO.EMIT_PAD, dtype=torch.uint8, device=dev)
             pad[:n].copy_(src)
             dst = torch.empty_like(src)
-            press = GO._Deflater(torch, dev, n)
+            press = GO.Deflater(torch, dev, n)
             ev = lambda: torch.cuda.Event(enable_timing=True)
             k_ms, c_ms = [], []
             for rep in range(args.reps + 2):

@@ -48,7 +48,7 @@ def main():
     param = OU.Param(200, asm['sigma'], None, io.StringIO())
     with OU.store_of(asm) as store:
         dev = store.device
-        em = GO._Emitter(asm['F'], param, store, 1)
+        em = GO.ScaffoldEmitter(asm['F'], param, store, 1)
         assert em.total == total
         out = torch.empty((total + 15) // 16 * 16, dtype=torch.uint8, device=dev)
         src = torch.empty_like(out)
@@ -65,7 +65,7 @@ def main():
             if rep >= 2:
                 emit_ms.append(a.elapsed_time(b))
                 copy_ms.append(b.elapsed_time(c))
-        assert em.key_error() is None
+        em.check()
         assert np.array_equal(out[:total].cpu().numpy(), want), 'emit_kernel output differs from the numpy model'
         emit_s, copy_s = float(np.median(emit_ms)) * 1e-3, float(np.median(copy_ms)) * 1e-3
         doc['emit_kernel'] = dict(ms=emit_s * 1e3, ms_min=min(emit_ms), ms_max=max(emit_ms), bytes_moved=2 * total,

@@ -47,7 +47,7 @@ def main():
     param = OU.Param(200, asm['sigma'], None, io.StringIO())
     with OU.store_of(asm) as store:
         dev = store.device
-        em = GO._Emitter(asm['F'], param, store, 1)
+        em = GO.ScaffoldEmitter(asm['F'], param, store, 1)
         ev = lambda: torch.cuda.Event(enable_timing=True)
         paths = [os.path.join(out_dir, n) for n in ('host.agp', 'host.gff', 'dev.agp', 'dev.gff')]
         host_s, dev_rounds = [], []
@@ -59,12 +59,11 @@ def main():
             t0 = time.time()
             text = GO._TextEmitter.make(em)
             assert text is not None
-            spent = [GO._write_fasta_chunks(text.file(which), path, GO.CHUNK_BYTES)
+            files = [GO.write_file(text.file(which), path, GO.CHUNK_BYTES)
                      for which, path in ((GO.TEXT_AGP, paths[2]), (GO.TEXT_GFF, paths[3]))]
-            text.finish()
             t_dev = time.time() - t0
-            kernels = text.measure_seconds + spent[0][0] + spent[1][0]
-            d2h, write = spent[0][1] + spent[1][1], spent[0][2] + spent[1][2]
+            kernels = text.measure_seconds + sum(f['emit_kernels'] for f in files)
+            d2h, write = sum(f['d2h'] for f in files), sum(f['file_write'] for f in files)
             totals = text.totals
             if rep >= 2:
                 host_s.append(t_host)
@@ -99,7 +98,7 @@ def main():
             if rep >= 2:
                 emit_ms.append(a.elapsed_time(b))
                 copy_ms.append(b.elapsed_time(c))
-        text.finish()
+        text.check()
         text.close()
         doc['text_emit_kernel'] = dict(bytes_written=total, ms=median(emit_ms), ms_min=min(emit_ms), ms_max=max(emit_ms),
                                        bytes_written_per_s=total / (median(emit_ms) * 1e-3), d2d_copy_ms=median(copy_ms),
@@ -119,7 +118,7 @@ def main():
             t0 = time.time()
             spent = GO.write_wrapped_fasta(store, rows, p_batch)
             batch_s.append(time.time() - t0)
-            kernel_ms.append(spent[0] * 1e3)
+            kernel_ms.append(spent['emit_kernels'] * 1e3)
         with open(p_fetch, 'rb') as fa, open(p_batch, 'rb') as fb:
             assert fa.read() == fb.read(), 'the wrapped FASTA differs from the per-contig writer'
         size = os.path.getsize(p_batch)
