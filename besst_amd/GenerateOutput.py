@@ -19,7 +19,9 @@ pipeline, :func:`write_chunks`: chunks cut by :func:`chunk_plan` go through two 
 copy and the file write of chunk c running while the kernels of chunk c + 1 do.
 ``SequenceStore.from_fasta`` fills the store from the contig
 FASTA itself (csrc/fasta.hip: the file's bytes are parsed in HBM by the rules of runBESST:45-74); ``C_dict`` then holds
-:class:`SequenceRef` handles instead of strings.  Like the rest of the package there is no CPU path: without
+:class:`SequenceRef` handles instead of strings.  A file that begins with the gzip magic is inflated first: a BGZF file
+(what ``--bgzf_outputs`` and ``bgzip`` write) on the device, block by block at its place in the text
+(:func:`_upload_bgzf_file`); any other gzip file by zlib on the host (:func:`_upload_gzip_host`).  Like the rest of the package there is no CPU path: without
 the library or a GPU these calls raise :class:`besst_amd._lib.BesstDeviceError`.
 """
 from __future__ import print_function
@@ -29,6 +31,7 @@ import io
 import os
 import time
 import warnings
+import zlib
 
 import numpy as np
 
@@ -223,19 +226,40 @@ class SequenceStore(object):
         objs = list(Contigs.values()) + list(small_contigs.values())
         return cls([c.name for c in objs], [c.sequence for c in objs], device=device)
 
+    inflate = None
+
     @classmethod
-    def from_fasta(cls, path, device=0, tile_bytes=None):
+    def from_fasta(cls, path, device=0, tile_bytes=None, blocks_per_launch=None):
         """The store of a contig FASTA, parsed on the device (csrc/fasta.hip) with the rules of the reference's
         ReadInContigseqs (runBESST:45-74): one row per header line in file order (``names``); ``index[name]`` is the row
         of the name's last occurrence.  ValueError: a byte outside ASCII, a header without a name, a contig of 2^31 bases
-        or more."""
+        or more.
+
+        A file whose first two bytes are the gzip magic (its name does not matter) is inflated on the way: on the device
+        if it is BGZF from its first byte to its last, at most ``blocks_per_launch`` blocks (BLOCKS_PER_LAUNCH) per launch,
+        by zlib on the host if it is any other gzip file or holds a block the device kernel does not take.  ``inflate``
+        of the store says which: None, 'device' or 'host'.  FastaError with the COMPRESSED offset of the block or member
+        at fault: a CRC-32 or ISIZE that is not the inflated bytes', a file that ends inside a member, bytes behind the
+        last member that are none, data zlib does not inflate.  The parser's own errors then count bytes of the
+        inflated text."""
         torch, dev = _torch_device(device)
+        with open(path, 'rb') as fh:
+            gz = fh.read(2) == GZIP_MAGIC
         with torch.cuda.device(dev):
-            text, n = _upload_file(torch, dev, path)
-            parsed = parse_fasta_text(text, n, tile_bytes)
+            if gz:
+                text, n, inflate = _upload_gzip_file(torch, dev, path, blocks_per_launch)
+            else:
+                (text, n), inflate = _upload_file(torch, dev, path), None
+            try:
+                parsed = parse_fasta_text(text, n, tile_bytes)
+            except FastaError as exc:
+                if inflate is None:
+                    raise
+                raise FastaError('%s (bytes of the inflated text: the file is compressed)' % exc, exc.offset)
             del text
         self = cls.__new__(cls)
         self.device = dev
+        self.inflate = inflate
         self._pool, self.pool_ptr, self.pool_bytes = parsed['pool'], parsed['pool'].data_ptr() + EMIT_PAD, parsed['pool_bytes']
         self._off, self._len = parsed['ctg_off'], parsed['ctg_len']
         self.offsets, self.lengths = self._off.cpu().numpy(), self._len.cpu().numpy()
@@ -393,6 +417,227 @@ def _upload_file(torch, dev, path):
             i += 1
         torch.cuda.current_stream(dev).wait_stream(copy)
         copy.synchronize()                                       # the pinned buffers are let go here
+    return text, n
+
+
+GZIP_MAGIC = b'\x1f\x8b'
+BLOCKS_PER_LAUNCH = 4096                 # BGZF blocks per launch of the inflate: four bytes of symbol workspace per inflated byte
+BGZF_WINDOW_BLOCKS = 1 << 16             # block descriptors a window's buffers hold (a window of more blocks is cut there)
+BGZF_DESC_BYTES = 24                     # include/besst_amd.h: sizeof(besst_bgzf_block)
+BGZF_MAX_BLOCK = 65536                   # a BGZF block's size in the file at most: the smallest window that holds a whole block
+BGZF_COMP_PAD = 4096                     # readable bytes the inflate wants behind the last payload
+BGZF_BAD_SIZE, BGZF_BAD_CRC = 9, 10      # include/besst_amd.h: BESST_BGZF_BAD_SIZE, BESST_BGZF_BAD_CRC
+
+
+def bgzf_walk(path, max_blocks=-1):
+    """The file as a chain of BGZF blocks (besst_bgzf_walk) -> (blocks, sum of their ISIZE, offset of the first byte that
+    is no whole BGZF block, size of the file); at most ``max_blocks`` blocks (< 0: all)."""
+    lib = _lib.load()
+    size = os.path.getsize(path)
+    n, inflated, end = _C.c_int64(0), _C.c_int64(0), _C.c_size_t(0)
+    if size:
+        data = np.memmap(path, dtype=np.uint8, mode='r')
+        _lib.check(lib.besst_bgzf_walk(_C.c_void_p(data.ctypes.data), int(data.shape[0]), int(max_blocks), _C.byref(n),
+                                       _C.byref(inflated), _C.byref(end)), 'besst_bgzf_walk')
+        size = int(data.shape[0])
+        del data
+    return n.value, inflated.value, end.value, size
+
+
+def _first_bad(word):
+    """The device's word of the first bad block -> (block, reason), or None"""
+    bad = int(word.item()) & NO_ERROR
+    return None if bad == NO_ERROR else (bad >> 8, bad & 0xff)
+
+
+def _upload_gzip_file(torch, dev, path, blocks_per_launch=None):
+    """A file that begins with the gzip magic -> (text, n, 'device' or 'host'), text as _upload_file leaves it."""
+    n_blocks, total, end, size = bgzf_walk(path)
+    if end == size:
+        got = _upload_bgzf_file(torch, dev, path, n_blocks, total, blocks_per_launch)
+        if got is not None:
+            return got[0], got[1], 'device'
+    text, n = _upload_gzip_host(torch, dev, path)
+    return text, n, 'host'
+
+
+def _upload_bgzf_file(torch, dev, path, n_blocks, total, blocks_per_launch=None):
+    """The sibling of _upload_file for a file that is ``n_blocks`` BGZF blocks of ``total`` inflated bytes and nothing else:
+    the file goes through two pinned buffers in windows, a window's block descriptors (besst_bgzf_scan_chunk) and
+    compressed bytes go up on the side stream, and the inflate of window c (besst_dev_bgzf_inflate: inflate, CRC-32,
+    first bad block) is enqueued while window c + 1 is read.  A block the window's end cuts is carried into the next
+    window.  Every block lands at its final place in the one text buffer; one synchronisation behind the last window
+    reads the first bad block.  -> (text, total), or None: the device kernel does not take a block's DEFLATE data (the
+    caller reads the file on the host).  FastaError: a block's CRC-32 or ISIZE is not its inflated bytes'."""
+    lib = _lib.load()
+    p = _C.c_void_p
+    per_launch = max(1, min(int(blocks_per_launch or BLOCKS_PER_LAUNCH), n_blocks))
+    ws_bytes = lib.besst_dev_bgzf_inflate_workspace_bytes(per_launch, min(per_launch * 65536, total))
+    if not ws_bytes:
+        raise ValueError('blocks_per_launch must lie in 1..2^24')
+    main = torch.cuda.current_stream(dev)
+    text = torch.empty(total + EMIT_PAD, dtype=torch.uint8, device=dev)
+    text[total:].zero_()
+    first_bad = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with open(path, 'rb', buffering=0) as fh:
+        size = os.fstat(fh.fileno()).st_size
+        cap = max(1, min(size, max(int(UPLOAD_CHUNK), BGZF_MAX_BLOCK)))   # a window: carried bytes + new ones, a whole block at least
+        desc_cap = max(2, min(BGZF_WINDOW_BLOCKS, n_blocks + (n_blocks & 1)))
+        desc_bytes = desc_cap * BGZF_DESC_BYTES                  # (a multiple of 16: the payloads' words stay aligned)
+        h_buf = [torch.empty(desc_bytes + cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        d_buf = [torch.zeros(desc_bytes + cap + BGZF_COMP_PAD, dtype=torch.uint8, device=dev) for _ in range(2)]
+        views = [memoryview(b.numpy()) for b in h_buf]
+        h_ptr = [b.data_ptr() for b in h_buf]
+        done, inflated_ev = [None, None], [None, None]
+        copy = torch.cuda.Stream(dev)
+        copy.wait_stream(main)
+        n, comp, inflated = _C.c_int64(0), _C.c_size_t(0), _C.c_int64(0)
+        file_at, blocks_at, dst_at, carry, i = 0, 0, 0, b'', 0
+        while file_at < size or carry:
+            slot = i % 2
+            if done[slot] is not None:
+                done[slot].synchronize()                        # the buffer's last copy has left it
+            window = views[slot][desc_bytes:]
+            have = len(carry)
+            window[:have] = carry
+            want = min(cap - have, size - file_at)
+            while want:
+                got = fh.readinto(window[have:have + want])
+                if not got:
+                    raise IOError('%s ended %d bytes early' % (path, size - file_at))
+                have, want, file_at = have + got, want - got, file_at + got
+            more = file_at < size
+            launches, at, nd = [], 0, 0                          # (first descriptor, blocks, inflated bytes) per launch
+            while at < have and nd < desc_cap:
+                _lib.check(lib.besst_bgzf_scan_chunk(p(h_ptr[slot] + desc_bytes), have, at, 1 if more else 0,
+                                                     min(per_launch, desc_cap - nd), 0, p(h_ptr[slot] + nd * BGZF_DESC_BYTES),
+                                                     _C.byref(n), _C.byref(comp), _C.byref(inflated)), 'besst_bgzf_scan_chunk')
+                if not n.value:
+                    break                                        # the window's end cuts the next block
+                launches.append((nd, n.value, inflated.value))
+                nd, at = nd + n.value, at + comp.value
+            if not launches:
+                raise IOError('%s changed while it was read' % path)
+            carry = bytes(window[at:have])
+            with torch.cuda.stream(copy):
+                if inflated_ev[slot] is not None:
+                    copy.wait_event(inflated_ev[slot])           # the launches that last read this device buffer
+                d_buf[slot][:nd * BGZF_DESC_BYTES].copy_(h_buf[slot][:nd * BGZF_DESC_BYTES], non_blocking=True)
+                d_buf[slot][desc_bytes:desc_bytes + at].copy_(h_buf[slot][desc_bytes:desc_bytes + at], non_blocking=True)
+                done[slot] = torch.cuda.Event()
+                done[slot].record(copy)
+            main.wait_event(done[slot])
+            d_ptr = d_buf[slot].data_ptr()
+            for d0, nb, nbytes in launches:
+                if blocks_at + nb > n_blocks or dst_at + nbytes > total:
+                    raise IOError('%s changed while it was read' % path)
+                _lib.check(lib.besst_dev_bgzf_inflate(p(main.cuda_stream), p(d_ptr + desc_bytes), p(d_ptr + d0 * BGZF_DESC_BYTES), nb,
+                                                      blocks_at, nbytes, p(text.data_ptr() + dst_at), p(ws.data_ptr()), ws_bytes,
+                                                      p(first_bad.data_ptr())), 'besst_dev_bgzf_inflate')
+                blocks_at, dst_at = blocks_at + nb, dst_at + nbytes
+            inflated_ev[slot] = torch.cuda.Event()
+            inflated_ev[slot].record(main)
+            i += 1
+        copy.synchronize()
+        main.synchronize()                                       # the pinned and the device buffers are let go here
+    if blocks_at != n_blocks or dst_at != total:
+        raise IOError('%s changed while it was read' % path)
+    bad = _first_bad(first_bad)
+    if bad is None:
+        return text, total
+    block, reason = bad
+    if reason not in (BGZF_BAD_SIZE, BGZF_BAD_CRC):
+        return None
+    offset = bgzf_walk(path, block)[2]
+    raise FastaError('the BGZF block at byte %d of the compressed FASTA file (block %d) is damaged: %s' % (
+        offset, block, 'its CRC-32 is not that of its inflated bytes' if reason == BGZF_BAD_CRC
+        else 'it does not inflate to ISIZE bytes'), offset)
+
+
+def _gzip_members(fh, piece=1 << 20):
+    """The inflated bytes of a file of gzip members, in pieces of at most ``piece`` bytes.  FastaError: the offset of the
+    member that zlib does not inflate (its data, CRC-32 or length), that the file's end cuts, or that is no gzip member."""
+    pending, pos, d, member_at = b'', 0, None, 0
+    while True:
+        if not pending:
+            pending = fh.read(piece)
+            if not pending:
+                break
+        if d is None:
+            d, member_at = zlib.decompressobj(31), pos
+        try:
+            out = d.decompress(pending, piece)
+        except zlib.error as exc:
+            raise FastaError('the gzip member at byte %d of the compressed FASTA file does not inflate: %s' % (member_at, exc),
+                             member_at)
+        rest = d.unused_data if d.eof else d.unconsumed_tail
+        pos += len(pending) - len(rest)
+        pending = rest
+        if d.eof:
+            d = None
+        if out:
+            yield out
+    while d is not None:                                         # (output zlib still holds when its input has run out)
+        out = d.decompress(b'', piece)
+        if not out:
+            break
+        yield out
+        if d.eof:
+            d = None
+    if d is not None:
+        raise FastaError('the compressed FASTA file ends inside the gzip member at byte %d' % member_at, member_at)
+
+
+def _upload_gzip_host(torch, dev, path):
+    """Any gzip file (several members, with or without BGZF's subfield), inflated by zlib on the host: the pieces are
+    streamed into two pinned buffers and uploaded as they fill; no copy of the whole text exists on the host.
+    -> (text, n) as _upload_file."""
+    size = max(1, min(int(UPLOAD_CHUNK), max(1 << 16, 4 * os.path.getsize(path))))
+    h_buf = [torch.empty(size, dtype=torch.uint8).pin_memory() for _ in range(2)]
+    views = [memoryview(b.numpy()) for b in h_buf]
+    done = [None, None]
+    main = torch.cuda.current_stream(dev)
+    copy = torch.cuda.Stream(dev)
+    copy.wait_stream(main)
+    parts, state = [], [0, 0]                                    # device pieces; [bytes in the buffer in use, buffers sent]
+
+    def send():
+        slot = state[1] % 2
+        part = torch.empty(state[0], dtype=torch.uint8, device=dev)
+        with torch.cuda.stream(copy):
+            part.copy_(h_buf[slot][:state[0]], non_blocking=True)
+            done[slot] = torch.cuda.Event()
+            done[slot].record(copy)
+        parts.append(part)
+        state[0], state[1] = 0, state[1] + 1
+        if done[state[1] % 2] is not None:
+            done[state[1] % 2].synchronize()                     # the next buffer's last copy has left it
+
+    try:
+        with open(path, 'rb') as fh:
+            for out in _gzip_members(fh):
+                at = 0
+                while at < len(out):
+                    take = min(len(out) - at, size - state[0])
+                    views[state[1] % 2][state[0]:state[0] + take] = out[at:at + take]
+                    state[0], at = state[0] + take, at + take
+                    if state[0] == size:
+                        send()
+        if state[0]:
+            send()
+    finally:
+        copy.synchronize()
+    main.wait_stream(copy)
+    n = sum(int(part.shape[0]) for part in parts)
+    text = torch.empty(n + EMIT_PAD, dtype=torch.uint8, device=dev)
+    text[n:].zero_()
+    at = 0
+    while parts:
+        part = parts.pop(0)
+        text[at:at + part.shape[0]].copy_(part)
+        at += int(part.shape[0])
+        del part
     return text, n
 
 

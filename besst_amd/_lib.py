@@ -238,6 +238,11 @@ _SIGNATURES = {
     'besst_dev_bgzf_deflate': (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_size_t, _P, C.c_size_t, _P, _P]),
     'besst_bgzf_deflate_device': (C.c_int, [C.c_int, _P, C.c_size_t, C.c_int32, C.c_int32, _P, C.c_size_t,
                                             C.POINTER(C.c_size_t)]),
+    'besst_bgzf_walk': (C.c_int, [_P, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
+    'besst_bgzf_scan_chunk': (C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_int32, C.c_int64, C.c_uint64, _P, C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
+    'besst_dev_bgzf_inflate_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
+    'besst_dev_bgzf_inflate': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

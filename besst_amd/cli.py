@@ -28,6 +28,7 @@ Every rank ingests its slice of each BAM on its own GPU and takes part in the li
 from __future__ import print_function
 
 import argparse
+import gzip
 import os
 import shutil
 import sys
@@ -39,9 +40,16 @@ from . import MakeScaffolds as MS
 from . import Parameter, bamio, libmetrics, mathstats_compat, session
 
 
+def open_fasta(path):
+    """The contig FASTA as text; a file that begins with the gzip magic (gzip, bgzip, --bgzf_outputs) through gzip."""
+    with open(path, 'rb') as fh:
+        magic = fh.read(2)
+    return gzip.open(path, 'rt') if magic == b'\x1f\x8b' else open(path)
+
+
 def read_fasta(path):
     seqs, name, chunks = {}, None, []
-    with open(path) as fh:
+    with open_fasta(path) as fh:
         for line in fh:
             if line.startswith('>'):
                 if name is not None:
@@ -57,7 +65,8 @@ def read_fasta(path):
 def build_parser():
     ap = argparse.ArgumentParser(prog='besst_amd.cli', description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('-c', dest='contigfile', required=True, help='contig FASTA')
+    ap.add_argument('-c', dest='contigfile', required=True,
+                    help='contig FASTA, plain or gzip / BGZF compressed (told by its first bytes, not its name)')
     ap.add_argument('-f', dest='bamfiles', nargs='+', required=True, help='one BAM per library')
     ap.add_argument('-o', dest='output', default='.', help='output directory')
     ap.add_argument('-orientation', dest='orientation', nargs='+', choices=['fr', 'rf'], required=True)
@@ -82,7 +91,8 @@ def build_parser():
     ap.add_argument('--fasta_on_gpu', dest='fasta_on_gpu', action='store_true',
                     help='read the contig FASTA on the GPU: the file goes to HBM as it is and is parsed there into the '
                          'sequence store (GenerateOutput.SequenceStore.from_fasta); the sequences do not pass through '
-                         'Python strings')
+                         'Python strings.  A BGZF file (bgzip, --bgzf_outputs) is inflated on the GPU too; any other gzip '
+                         'file by zlib on the host')
     ap.add_argument('--outputs_on_gpu', dest='outputs_on_gpu', action='store_true',
                     help='format info-pass<n>.agp / .gff on the GPU, and write repeats.fa / low_coverage_contigs.fa '
                          'from the sequence store in one go where the contigs live there (--fasta_on_gpu)')

@@ -1245,6 +1245,23 @@ __global__ __launch_bounds__(256) void bgzf_crc_kernel(const uint8_t* __restrict
     }
 }
 
+static_assert(kInfSizeMismatch == BESST_BGZF_BAD_SIZE && kInfCrcMismatch == BESST_BGZF_BAD_CRC, "besst_amd.h names these two statuses");
+
+// What a reader of a whole file wants of the statuses: the first block that is not good, and why - one 64-bit word that
+// stays on the device from launch to launch, so that the host reads eight bytes per file, not a status array per launch.
+__global__ __launch_bounds__(256) void bgzf_first_bad_kernel(const uint32_t* __restrict__ status, uint32_t n_blocks,
+                                                             unsigned long long block_base, unsigned long long* first_bad) {
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t st = b < n_blocks ? status[b] : (uint32_t)kInfOk;
+    unsigned long long v = st != kInfOk ? ((block_base + b) << 8) | (st & 0xffu) : ~0ull;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long o = __shfl_xor(v, d, 64);
+        v = o < v ? o : v;
+    }
+    if ((threadIdx.x & 63u) == 0u && v != ~0ull) atomicMin(first_bad, v);    // (a wave without a bad block - nearly all - is silent)
+}
+
 namespace {
 
 __device__ __forceinline__ uint32_t ld32u(const uint8_t* p) {     // little-endian dword at any alignment
@@ -1606,6 +1623,14 @@ int launch_bgzf_inflate(hipStream_t s, const uint8_t* src, const BgzfBlock* bloc
         }
     }
     hipLaunchKernelGGL(bgzf_crc_kernel, dim3(n_blocks), dim3(256), 0, s, dst, blocks, n_blocks, status);
+    BESST_HIP_TRY(hipGetLastError());
+    return BESST_OK;
+}
+
+int launch_bgzf_first_bad(hipStream_t s, const uint32_t* status, uint32_t n_blocks, uint64_t block_base, uint64_t* first_bad) {
+    if (n_blocks == 0) return BESST_OK;
+    hipLaunchKernelGGL(bgzf_first_bad_kernel, dim3((n_blocks + 255u) / 256u), dim3(256), 0, s, status, n_blocks,
+                       (unsigned long long)block_base, reinterpret_cast<unsigned long long*>(first_bad));
     BESST_HIP_TRY(hipGetLastError());
     return BESST_OK;
 }

@@ -70,6 +70,29 @@ inline bool scan_bgzf_chunk(const uint8_t* map, size_t map_len, size_t* fpos, si
     return true;
 }
 
+// A whole byte range as a chain of BGZF blocks, by scan_bgzf_chunk's rules (any further extra subfields behind BC, empty
+// blocks anywhere, no EOF block needed): the blocks up to the first byte that is no whole BGZF block, max_blocks at most.
+// `end` equals map_len when the range is BGZF to its last byte.  What sizes a reader's buffers and tells it, before
+// anything is allocated, whether the device inflate can take the file.
+struct BgzfWalk {
+    uint64_t n_blocks, inflated_bytes;
+    size_t end;
+};
+inline BgzfWalk walk_bgzf(const uint8_t* map, size_t map_len, uint64_t max_blocks = ~(uint64_t)0) {
+    BgzfWalk w{0, 0, 0};
+    while (w.n_blocks < max_blocks && w.end < map_len) {
+        BgzfBlock b;
+        uint32_t n = 0;
+        size_t at = w.end, comp = 0, inflated = 0;
+        // (more_follows: a block cut by the end of the range ends the walk like any other byte that is no block)
+        if (!scan_bgzf_chunk(map, map_len, &at, 1, ~(size_t)0, &b, &n, &comp, &inflated, true, 0, true) || n == 0) break;
+        w.n_blocks += 1;
+        w.inflated_bytes += inflated;
+        w.end = at;
+    }
+    return w;
+}
+
 // First BGZF block boundary at or behind `from`: the gzip magic with the BC subfield, a plausible BSIZE, and two further
 // blocks (or the end of the file) chained behind it - payload bytes that happen to spell a header do not survive that.
 inline size_t find_bgzf_boundary(const uint8_t* map, size_t map_len, size_t from) {

@@ -56,6 +56,9 @@ struct BamColumns {
 int launch_bgzf_inflate(hipStream_t s, const uint8_t* src, const BgzfBlock* blocks, uint32_t n_blocks, uint8_t* dst,
                         uint32_t* status, uint32_t* symbols = nullptr);
 size_t bgzf_inflate_symbol_places(size_t inflated_bytes, size_t n_blocks);
+// the statuses of n_blocks blocks reduced into *first_bad: the minimum of what it holds and (block_base + b) << 8 | status[b]
+// over the blocks whose status is not 0
+int launch_bgzf_first_bad(hipStream_t s, const uint32_t* status, uint32_t n_blocks, uint64_t block_base, uint64_t* first_bad);
 // modes of a chunk's walk: the first start of the chunk is a guess nobody vouches for (the first chunk of a part of the
 // file whose entry is not known yet) / only the record in the tail slot counts (the blocks behind a part's end, inflated
 // for the bytes of the part's last record); summary: 12 words (bgzf_gpu.hip)

@@ -939,4 +939,63 @@ int besst_bgzf_inflate_device(int device, const void* bgzf, size_t n_bytes, void
     return BESST_OK;
 }
 
+int besst_bgzf_walk(const void* bgzf, size_t n_bytes, int64_t max_blocks, int64_t* n_blocks, int64_t* inflated_bytes, size_t* end) {
+    BESST_REQUIRE((bgzf || n_bytes == 0) && n_blocks && inflated_bytes && end, "bgzf_walk: null pointer");
+    const BgzfWalk w = walk_bgzf(static_cast<const uint8_t*>(bgzf), n_bytes, max_blocks < 0 ? ~(uint64_t)0 : (uint64_t)max_blocks);
+    *n_blocks = (int64_t)w.n_blocks;
+    *inflated_bytes = (int64_t)w.inflated_bytes;
+    *end = w.end;
+    return BESST_OK;
+}
+
+static_assert(sizeof(besst_bgzf_block) == sizeof(BgzfBlock) && offsetof(besst_bgzf_block, src_len) == offsetof(BgzfBlock, src_len) &&
+                  offsetof(besst_bgzf_block, dst_off_lo) == offsetof(BgzfBlock, dst_off_lo) &&
+                  offsetof(besst_bgzf_block, dst_off_hi) == offsetof(BgzfBlock, dst_off_hi) &&
+                  offsetof(besst_bgzf_block, dst_len) == offsetof(BgzfBlock, dst_len) && offsetof(besst_bgzf_block, crc) == offsetof(BgzfBlock, crc),
+              "besst_bgzf_block is BgzfBlock");
+
+int besst_bgzf_scan_chunk(const void* window, size_t n_bytes, size_t from, int32_t more_follows, int64_t max_blocks, uint64_t dst0,
+                          besst_bgzf_block* blocks, int64_t* n_blocks, size_t* comp_bytes, int64_t* inflated_bytes) {
+    BESST_REQUIRE((window || n_bytes == 0) && n_blocks && comp_bytes && inflated_bytes && (blocks || max_blocks == 0), "bgzf_scan_chunk: null pointer");
+    BESST_REQUIRE(from <= n_bytes && n_bytes <= 0xFFFFFFFFull && max_blocks >= 0 && max_blocks <= 0x7FFFFFFF, "bgzf_scan_chunk: sizes out of range");
+    BgzfBlock* out = reinterpret_cast<BgzfBlock*>(blocks);
+    size_t at = from, comp = 0, inflated = 0;
+    uint32_t n = 0;
+    if (!scan_bgzf_chunk(static_cast<const uint8_t*>(window), n_bytes, &at, (size_t)max_blocks, ~(size_t)0, out, &n, &comp, &inflated,
+                         more_follows != 0, (size_t)dst0, true)) {
+        set_error("bgzf_scan_chunk: no whole BGZF block where one should begin");
+        return BESST_ERR_ARG;
+    }
+    for (uint32_t b = 0; b < n; ++b) out[b].src_off += (uint32_t)from;   // (from the window's first byte: the payloads' words stay aligned)
+    *n_blocks = (int64_t)n;
+    *comp_bytes = comp;
+    *inflated_bytes = (int64_t)inflated;
+    return BESST_OK;
+}
+
+// workspace of a launch: the blocks' status words, then the second form's symbols
+static size_t inflate_status_bytes(int64_t n_blocks) { return align_up((size_t)n_blocks * 4, 256); }
+
+size_t besst_dev_bgzf_inflate_workspace_bytes(int64_t n_blocks, int64_t inflated_bytes) {
+    if (n_blocks < 0 || n_blocks > ((int64_t)1 << 24) || inflated_bytes < 0 || inflated_bytes > n_blocks * 65536) return 0;
+    return inflate_status_bytes(n_blocks) + 4 * bgzf_inflate_symbol_places((size_t)inflated_bytes, (size_t)n_blocks);
+}
+
+int besst_dev_bgzf_inflate(void* stream, const void* comp, const besst_bgzf_block* blocks, int64_t n_blocks, int64_t block_base,
+                           int64_t inflated_bytes, void* dst, void* workspace, size_t workspace_bytes, uint64_t* first_bad) {
+    BESST_REQUIRE(comp && blocks && dst && workspace && first_bad, "dev_bgzf_inflate: null pointer");
+    BESST_REQUIRE(block_base >= 0 && block_base < ((int64_t)1 << 55), "dev_bgzf_inflate: block_base out of range");
+    const size_t need = besst_dev_bgzf_inflate_workspace_bytes(n_blocks, inflated_bytes);
+    BESST_REQUIRE(need != 0, "dev_bgzf_inflate: n_blocks or inflated_bytes out of range");
+    BESST_REQUIRE(workspace_bytes >= need, "dev_bgzf_inflate: workspace too small");
+    BESST_REQUIRE(((uintptr_t)comp & 3u) == 0 && ((uintptr_t)workspace & 15u) == 0, "dev_bgzf_inflate: comp or workspace misaligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint32_t* status = static_cast<uint32_t*>(workspace);
+    uint32_t* symbols = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + inflate_status_bytes(n_blocks));
+    if (int rc = launch_bgzf_inflate(s, static_cast<const uint8_t*>(comp), reinterpret_cast<const BgzfBlock*>(blocks), (uint32_t)n_blocks,
+                                     static_cast<uint8_t*>(dst), status, symbols))
+        return rc;
+    return launch_bgzf_first_bad(s, status, (uint32_t)n_blocks, (uint64_t)block_base, first_bad);
+}
+
 }  // extern "C"

@@ -40,7 +40,9 @@ extern "C" {
  * (additions only): the scaffold-output entry points besst_{dev,host}_seq_overlaps / besst_{dev,host}_emit_scaffolds; the
  * FASTA reader besst_dev_fasta_workspace_bytes / besst_dev_fasta_scan / besst_dev_fasta_pack; the text of the output stage
  * besst_dev_text_workspace_bytes / besst_dev_text_measure / besst_dev_text_emit / besst_dev_wrap_fasta,
- * besst_dev_bgzf_deflate_bound / besst_dev_bgzf_deflate_workspace_bytes / besst_dev_bgzf_deflate / besst_bgzf_deflate_device. */
+ * besst_dev_bgzf_deflate_bound / besst_dev_bgzf_deflate_workspace_bytes / besst_dev_bgzf_deflate / besst_bgzf_deflate_device;
+ * the inflate of a BGZF file in device memory besst_bgzf_walk / besst_bgzf_scan_chunk /
+ * besst_dev_bgzf_inflate_workspace_bytes / besst_dev_bgzf_inflate. */
 #define BESST_ABI_VERSION 3
 
 /* status codes */
@@ -246,6 +248,47 @@ int besst_ctx_push_bam_device_slice(besst_ctx* ctx, besst_bam* bam, int32_t part
  * concatenated in out (capacity out_cap, length in *out_len).  BESST_ERR_UNSUPPORTED when a block does not inflate
  * (its index and status in besst_last_error()). */
 int besst_bgzf_inflate_device(int device, const void* bgzf, size_t n_bytes, void* out, size_t out_cap, size_t* out_len);
+
+/* ---- BGZF inflate from device memory into device memory (csrc/bgzf_gpu.hip; GenerateOutput.py: SequenceStore.from_fasta) --
+ * What a BGZF block is here (csrc/bgzf_scan.h): a gzip member with FEXTRA whose FIRST extra subfield is BC (further
+ * subfields may follow it), BSIZE that fits, ISIZE <= 65536.  Empty blocks may stand anywhere; no EOF block is needed.
+ *   besst_bgzf_walk        (host, no GPU) the chain of blocks from bgzf[0] on, max_blocks at most (< 0: all): their number,
+ *                          the sum of their ISIZE, and *end: the offset of the first byte that is no whole BGZF block
+ *                          (n_bytes: the range is BGZF to its last byte).  Always BESST_OK but for null pointers.
+ *   besst_bgzf_scan_chunk  (host, no GPU) the descriptors of the blocks of window[from, n_bytes), max_blocks at most, laid
+ *                          back to back from inflated offset dst0 on; src_off counts from window[0].  more_follows != 0:
+ *                          the window is a part of a file and a block cut by its end stops the scan in front of it
+ *                          (0: such a block is an error).  *comp_bytes: bytes of the window the blocks take, from `from`.
+ *                          BESST_ERR_ARG: bytes that are no BGZF block where one should begin (the counts are not
+ *                          written; `blocks` may hold the blocks in front of that place).
+ *   besst_dev_bgzf_inflate_workspace_bytes  status words and symbol buffer of one launch of n_blocks blocks (<= 2^24) that
+ *                          inflate to inflated_bytes (<= 65536 n_blocks); 0: arguments out of range.
+ *   besst_dev_bgzf_inflate enqueues on `stream`: the inflate of the n_blocks blocks (device descriptors; payloads in comp,
+ *                          4-byte aligned, with 4096 readable bytes behind the last payload) to dst + their dst_off, every
+ *                          dst_off + dst_len within inflated_bytes; the CRC-32 check; and the reduction of the blocks'
+ *                          statuses into *first_bad (device): the minimum, over this and every earlier launch, of
+ *                          (block_base + index of the block) << 8 | reason - reason 1..8: the DEFLATE data is not what the
+ *                          kernel takes, BESST_BGZF_BAD_SIZE: inflated length != ISIZE, BESST_BGZF_BAD_CRC.  The caller
+ *                          sets *first_bad to all ones once per file; it still is when every block was good.  Up to 15
+ *                          bytes in front of dst + dst_off (never across a 16-byte boundary) and behind the block's end
+ *                          are read by the CRC check and not used.  BESST_ERR_ARG without touching the device: a null
+ *                          pointer, n_blocks or block_base < 0, sizes out of range, a workspace smaller than asked for. */
+#define BESST_BGZF_BAD_SIZE 9
+#define BESST_BGZF_BAD_CRC 10
+typedef struct besst_bgzf_block {
+    uint32_t src_off, src_len;       /* the DEFLATE payload in the compressed bytes */
+    uint32_t dst_off_lo, dst_off_hi; /* where its inflated bytes go */
+    uint32_t dst_len, crc;           /* ISIZE and CRC-32 of the gzip trailer */
+} besst_bgzf_block;
+int besst_bgzf_walk(const void* bgzf, size_t n_bytes, int64_t max_blocks, int64_t* n_blocks, int64_t* inflated_bytes,
+                    size_t* end);
+int besst_bgzf_scan_chunk(const void* window, size_t n_bytes, size_t from, int32_t more_follows, int64_t max_blocks,
+                          uint64_t dst0, besst_bgzf_block* blocks, int64_t* n_blocks, size_t* comp_bytes,
+                          int64_t* inflated_bytes);
+size_t besst_dev_bgzf_inflate_workspace_bytes(int64_t n_blocks, int64_t inflated_bytes);
+int besst_dev_bgzf_inflate(void* stream, const void* comp, const besst_bgzf_block* blocks, int64_t n_blocks,
+                           int64_t block_base, int64_t inflated_bytes, void* dst, void* workspace, size_t workspace_bytes,
+                           uint64_t* first_bad);
 
 /* libmetrics sampling (replaces the three `for read in bam_file` scans, libmetrics.py:63,257,293).
  * top_mask[tid] != 0 marks the 1000 longest references.  orientation/min_mapq/read_len as in

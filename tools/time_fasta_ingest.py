@@ -7,7 +7,10 @@
     the two alternating;
   * wall time of SequenceStore.from_fasta (file -> pinned buffers -> HBM -> kernels -> store);
   * wall time of the host path (cli.read_fasta + SequenceStore(names, sequences)) in the same process on the same file,
-    in both orders, the page cache warm for both.
+    in both orders, the page cache warm for both;
+  * the same file compressed: as BGZF by GenerateOutput.bgzf_compress (from_fasta inflates it on the device) and by zlib
+    at level 1 as one plain gzip member (from_fasta inflates it on the host) - wall time of from_fasta on the three files,
+    alternating, --gz_reps rounds, with the bytes each form sends over PCIe; and cli.read_fasta on the BGZF file.
 
     python tools/time_fasta_ingest.py --out profiles/fasta_ingest.json
 """
@@ -18,6 +21,7 @@ import os
 import sys
 import tempfile
 import time
+import zlib
 
 import numpy as np
 
@@ -58,11 +62,66 @@ def host_path(path):
     return store, t1 - t0, time.time() - t1
 
 
+def write_compressed(path, work):
+    """-> {'bgzf': path, 'gzip': path} of the FASTA at ``path``"""
+    with open(path, 'rb') as fh:
+        raw = fh.read()
+    out = dict(bgzf=os.path.join(work, 'contigs.bgzf.fa.gz'), gzip=os.path.join(work, 'contigs.gzip.fa.gz'))
+    with open(out['bgzf'], 'wb') as fh:
+        fh.write(GO.bgzf_compress(raw))
+    comp = zlib.compressobj(1, zlib.DEFLATED, 31)
+    with open(out['gzip'], 'wb') as fh:
+        for at in range(0, len(raw), 64 << 20):
+            fh.write(comp.compress(raw[at:at + (64 << 20)]))
+        fh.write(comp.flush())
+    return out
+
+
+def compressed_runs(path, n, asm, reps, work):
+    """from_fasta on the plain, the BGZF and the gzip file, alternating; cli.read_fasta on the BGZF file"""
+    files = dict(write_compressed(path, work), plain=path)
+    try:
+        n_blocks = GO.bgzf_walk(files['bgzf'])[0]
+        doc = dict(file_bytes={k: os.path.getsize(v) for k, v in files.items()}, bgzf_blocks=n_blocks,
+                   # what crosses PCIe on the way in: the file (and 24 bytes of descriptor per block), or the inflated text
+                   pcie_bytes=dict(plain=n, bgzf=os.path.getsize(files['bgzf']) + GO.BGZF_DESC_BYTES * n_blocks, gzip=n),
+                   from_fasta_s=dict(plain=[], bgzf=[], gzip=[]), inflate={})
+        for k in files.values():
+            with open(k, 'rb') as fh:                            # page cache warm
+                while fh.read(64 << 20):
+                    pass
+        for rep in range(reps):
+            for kind in ('plain', 'bgzf', 'gzip'):
+                store, took = device_path(files[kind])
+                doc['from_fasta_s'][kind].append(took)
+                doc['inflate'][kind] = store.inflate
+                if rep == 0:
+                    assert store.names == asm['names'] and np.array_equal(store.lengths, asm['lengths'])
+                    got = store._pool[GO.EMIT_PAD:GO.EMIT_PAD + store.pool_bytes].cpu().numpy()
+                    assert np.array_equal(got, asm['pool']), 'the parsed pool of the %s file differs from the assembly' % kind
+                    del got
+                store.close()
+                del store
+        doc['from_fasta_s_median'] = {k: float(np.median(v)) for k, v in doc['from_fasta_s'].items()}
+        t0 = time.time()
+        seqs = cli.read_fasta(files['bgzf'])
+        doc['read_fasta_bgzf_s'] = time.time() - t0
+        assert list(seqs) == asm['names']
+        del seqs
+        doc['reps'] = reps
+        return doc
+    finally:
+        for kind in ('bgzf', 'gzip'):
+            if os.path.exists(files[kind]):
+                os.remove(files[kind])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'fasta_ingest.json'))
     ap.add_argument('--contigs', type=int, default=100_000)
     ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--gz_reps', type=int, default=3, help='rounds of from_fasta over the plain, BGZF and gzip file')
     args = ap.parse_args()
     import torch
     asm = OU.seeded_assembly(args.contigs, 3000, 20000, 17)
@@ -97,6 +156,7 @@ def main():
             walls.append(run)
         doc['wall'] = walls
         doc['verified_vs_assembly'] = True
+        doc['compressed'] = compressed_runs(path, n, asm, args.gz_reps, work)
         # the kernels alone, on the bytes in HBM
         dev = torch.device('cuda', 0)
         text, _ = GO._upload_file(torch, dev, path)
