@@ -37,7 +37,7 @@ def assert_table_equals_c_oracle(table, aligned, ctr, batch, wl):
     # properties that hold at any size
     assert np.all(np.diff(table.key.astype(np.uint64)) > 0)                      # strictly sorted, unique keys
     assert int(table.n.sum()) == ctr.n_tuples                                     # every tuple lands in one row
-    assert np.array_equal(np.cumsum(np.r_[0, table.n[:-1]]), table.offset)        # slices tile the arrays
+    assert np.array_equal(np.cumsum(np.r_[0, table.n])[:-1], table.offset)        # slices tile the arrays (no row: no slice)
     o = table.obs_lo.astype(np.int64) + table.obs_hi
     assert int(table.sum_obs[link].sum()) == int(o.sum())
     assert int(table.sum_obs_sq[link].sum()) == int((o * o).sum())
