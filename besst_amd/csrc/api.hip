@@ -172,7 +172,7 @@ void besst_ctx_destroy(besst_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     c->table.release(); c->aligned.release();
     c->tid.release(); c->mtid.release(); c->pos.release(); c->mpos.release(); c->tlen.release();
-    c->flag.release(); c->qlen.release(); c->mapq.release(); c->mate_bits.release();
+    c->flag.release(); c->qlen.release(); c->mapq.release(); c->mate_bits.release(); c->tid_bits.release();
     c->keys.release(); c->payload.release(); c->row_key.release();
     c->row_mask.release(); c->row_n.release(); c->row_first.release(); c->row_offset.release();
     c->row_sum.release(); c->row_sum_sq.release(); c->obs_lo.release(); c->obs_hi.release();
@@ -264,6 +264,7 @@ int besst_ctx_clear_records(besst_ctx* c) {
     BESST_REQUIRE(c, "null context");
     c->n_records = 0;
     c->bits_upto = 0;
+    c->tid_bits_upto = 0;
     c->built = false;
     return BESST_OK;
 }
@@ -426,6 +427,7 @@ static int fill_classify_args(ClassifyArgs& a, int64_t n, const int32_t* tid, co
     a.no_score = p->no_score;
     a.record_path = p->record_path;
     a.mate_bits = static_cast<const uint8_t*>(p->mate_bits);
+    a.tid_bits = p->mate_bits ? static_cast<const uint8_t*>(p->tid_bits) : nullptr;   // (only honoured together)
     a.ps_table = nullptr; a.ps_rows = 0; a.ps_shift = 0; a.ps_base = 0;
     BESST_REQUIRE(p->record_path == 0 || p->record_path == 1, "classify: record_path must be 0 or 1");
     return BESST_OK;
@@ -670,7 +672,16 @@ int besst_dev_mate_bits(void* stream, int64_t n, const int32_t* tid, const int32
     if (n == 0) return BESST_OK;
     BESST_REQUIRE(tid && mtid && bits, "dev_mate_bits: null pointer");
     BESST_REQUIRE(aligned16(tid) && aligned16(mtid), "dev_mate_bits: columns must be 16-byte aligned");
-    return launch_mate_bits(static_cast<hipStream_t>(stream), tid, mtid, 0, n, n, static_cast<uint8_t*>(bits));
+    return launch_mate_bits(static_cast<hipStream_t>(stream), tid, mtid, 0, n, n, static_cast<uint8_t*>(bits), nullptr);
+}
+
+int besst_dev_record_bits(void* stream, int64_t n, const int32_t* tid, const int32_t* mtid, void* mate_bits, void* tid_bits) {
+    BESST_REQUIRE(n >= 0, "dev_record_bits: negative record count");
+    if (n == 0) return BESST_OK;
+    BESST_REQUIRE(tid && mtid && mate_bits && tid_bits, "dev_record_bits: null pointer");
+    BESST_REQUIRE(aligned16(tid) && aligned16(mtid), "dev_record_bits: columns must be 16-byte aligned");
+    return launch_mate_bits(static_cast<hipStream_t>(stream), tid, mtid, 0, n, n, static_cast<uint8_t*>(mate_bits),
+                            static_cast<uint8_t*>(tid_bits));
 }
 
 size_t besst_dev_lognormal_tables_workspace_bytes(int64_t x_max) { return lognormal_tables_workspace_bytes(x_max); }
@@ -745,19 +756,35 @@ int besst_ctx_build_graph(besst_ctx* c) {
     {   // the mate-elsewhere bits of the records that have none yet (everything pushed since the last build): 8 bytes read
         // per record once, after which every pass over these records leaves `mtid` alone where tid == mtid.
         // BESST_MATE_BITS=0 (tests): the loop compares the columns itself.
+        // The run bits (record i lies on another reference than record i - 1) are made in the same pass and extended with
+        // them: a push's first record is compared with the resident record before it.  BESST_TID_BITS=0: only the mate
+        // bits, the fused loop reads `tid` of every record.
         const char* off = getenv("BESST_MATE_BITS");
+        const char* tid_off = getenv("BESST_TID_BITS");
         lp.mate_bits = nullptr;
+        lp.tid_bits = nullptr;
         if (!(off && off[0] == '0' && off[1] == 0) && n > 0) {
+            const bool runs = !(tid_off && tid_off[0] == '0' && tid_off[1] == 0);
             const size_t need = (size_t)((n + 7) / 8) + 16;
             if (need > c->mate_bits.cap) {                   // (growing drops what was there)
                 if ((rc = c->mate_bits.ensure(need + need / 2))) return rc;
                 c->bits_upto = 0;
             }
-            if (c->bits_upto < n) {
-                if ((rc = launch_mate_bits(c->stream, c->tid.p, c->mtid.p, c->bits_upto, n, n, c->mate_bits.p))) return rc;
+            if (runs && need > c->tid_bits.cap) {
+                if ((rc = c->tid_bits.ensure(need + need / 2))) return rc;
+                c->tid_bits_upto = 0;
+            }
+            // (one launch writes both planes from the shorter of the two: they differ only after a build without run bits)
+            const int64_t upto = runs && c->tid_bits_upto < c->bits_upto ? c->tid_bits_upto : c->bits_upto;
+            if (upto < n) {
+                if ((rc = launch_mate_bits(c->stream, c->tid.p, c->mtid.p, upto, n, n, c->mate_bits.p,
+                                           runs ? c->tid_bits.p : nullptr)))
+                    return rc;
                 c->bits_upto = n;
+                if (runs) c->tid_bits_upto = n;
             }
             lp.mate_bits = c->mate_bits.p;
+            if (runs) lp.tid_bits = c->tid_bits.p;
         }
     }
     rc = besst_dev_classify(c->stream, n, c->tid.p, c->mtid.p, c->pos.p, c->mpos.p, c->flag.p, c->mapq.p, c->qlen.p,

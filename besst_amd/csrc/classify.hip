@@ -624,7 +624,11 @@ __device__ __forceinline__ int wave_sum_dpp(int v) {     // the sum in every lan
 // for the open runs the lanes hold - so the cost is per distinct key and round, not per tuple; no LDS, three registers.
 // kBits: ClassifyArgs::mate_bits is there - `mtid` moves from the columns every record is read from to the columns that only
 // the lanes with a candidate read (pos / mpos / flag): 4 of a record's 11 always-read bytes become 1/8.
-template <bool kRuns, bool kBits>
+// kBits == 2: ClassifyArgs::tid_bits is there as well - in a (tid, pos)-sorted stream `tid` changes once in thousands of
+// records, and the loop read every one of them to find that a sub-tile's 256 equal its first.  With the run bits a full
+// block reads the `tid` of a sub-tile only when one of its records differs from the record before it; elsewhere the
+// contig is the one the wave carries (cur_tid).  `tid` leaves the always-read columns: 4 of 7 1/8 bytes become 1/8.
+template <bool kRuns, int kBits>
 __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
     ClassifyArgs a, unsigned long long* __restrict__ aligned, uint64_t* __restrict__ seg_keys,
     uint64_t* __restrict__ seg_payload, SummView summ, uint32_t* __restrict__ run_status) {
@@ -698,6 +702,7 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
     int32_t run_tid = -1;                                 // the wave's running coverage (uniform)
     int run_sum = 0;
     int q_head = 0, q_count = 0;                          // the queue of candidates not yet evaluated (uniform)
+    constexpr bool kTid = kBits == 2;
     // the chain's state (uniform): the last record of the block so far that reached CreateEdge, where the next tuple goes,
     // and the block's first reaching record (the one stitch_kernel resolves against the blocks before)
     int st_known = 0, st_p1 = 0, st_p2 = 0, st_emit = 0;
@@ -978,8 +983,8 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         // number of outstanding loads is the same on every path and the waits the compiler places are exact.
         // (the byte and halfword columns stay packed as they were loaded - one and two registers - until process() takes
         // them apart: three sub-tiles of columns are live at once)
-        struct ColsA { int4 tid, mtid; uint32_t mapq; uint2 qlen; uint32_t bits; };     // (kBits: mtid unused, else bits)
-        struct ColsC { int4 pos, mpos, mtid; uint2 flag; };                              // (mtid: kBits only)
+        struct ColsA { int4 tid, mtid; uint32_t mapq; uint2 qlen; uint32_t bits; };     // (kBits: mtid unused, else bits; kTid: tid unused)
+        struct ColsC { int4 pos, mpos, mtid, tid; uint2 flag; };                         // (mtid: kBits only, tid: kTid only)
         // Addresses: the block's first record of every column is a uniform pointer (a scalar register pair), a lane adds
         // a 32-bit offset to it (the saddr + voffset form of the load) - as 64-bit pointers per lane and column the seven
         // columns held fourteen vector registers through the loop, and the loop spilled.
@@ -991,6 +996,7 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         const uint8_t* const b_mapq = a.mapq + block_base;
         const uint16_t* const b_qlen = a.qlen + block_base;
         const uint8_t* const b_bits = kBits ? a.mate_bits + (block_base >> 3) : nullptr;
+        const uint8_t* const b_tbits = kTid ? a.tid_bits + (block_base >> 3) : nullptr;
         typedef int v4i __attribute__((ext_vector_type(4)));
         auto load_a = [&](int st) {
             const uint32_t li = (uint32_t)st * (uint32_t)(kFwSub / 4) + (uint32_t)lane;   // the lane's group of four records
@@ -998,12 +1004,15 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
 #ifndef BESST_FW_PLAIN_LOADS
             // (non-temporal: every record is read once - marking these four streams so took 2.3 % off the kernel; the same
             // mark on the candidate columns, where idle lanes re-read one sector, or on the segment stores made it slower)
-            const v4i t4 = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(b_tid) + li);
+            // (kTid: `tid` is a candidate column - load_c -; here the lane takes its nibble of the run bits, bits 4-7)
+            v4i t4 = {0, 0, 0, 0};
+            if constexpr (!kTid) t4 = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(b_tid) + li);
             v4i m4 = t4;
             v.bits = 0u;
             if constexpr (kBits) {
                 // (the lane's four records begin at block_base + 4 li: their bits are a nibble of byte li / 2 of the block's)
                 v.bits = ((uint32_t)b_bits[li >> 1] >> ((li & 1u) * 4u)) & 15u;
+                if constexpr (kTid) v.bits |= (((uint32_t)b_tbits[li >> 1] >> ((li & 1u) * 4u)) & 15u) << 4;
             } else {
                 m4 = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(b_mtid) + li);
             }
@@ -1015,11 +1024,13 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
             v.mapq = q1;
             v.qlen = make_uint2(q4.x, q4.y);
 #else
-            v.tid = reinterpret_cast<const int4*>(b_tid)[li];
+            v.tid = make_int4(0, 0, 0, 0);
+            if constexpr (!kTid) v.tid = reinterpret_cast<const int4*>(b_tid)[li];
             v.bits = 0u;
             if constexpr (kBits) {
                 v.mtid = v.tid;
                 v.bits = ((uint32_t)b_bits[li >> 1] >> ((li & 1u) * 4u)) & 15u;
+                if constexpr (kTid) v.bits |= (((uint32_t)b_tbits[li >> 1] >> ((li & 1u) * 4u)) & 15u) << 4;
             } else {
                 v.mtid = reinterpret_cast<const int4*>(b_mtid)[li];
             }
@@ -1029,7 +1040,7 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
             return v;
         };
         auto load_c = [&](int st, const ColsA& v) {
-            const bool need = kBits ? v.bits != 0u
+            const bool need = kBits ? (v.bits & 15u) != 0u
                                     : (v.tid.x != v.mtid.x || v.tid.y != v.mtid.y || v.tid.z != v.mtid.z || v.tid.w != v.mtid.w);
             // (a lane without a candidate reads the first 16 bytes of the BLOCK's columns - one sector per column and block,
             // in cache after its first use - and not its sub-tile's first sector, which nobody else may want: 0.3 GB less
@@ -1041,6 +1052,15 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
             c.flag = reinterpret_cast<const uint2*>(b_flag)[li];
             if constexpr (kBits) c.mtid = reinterpret_cast<const int4*>(b_mtid)[li];
             else c.mtid = v.mtid;
+            c.tid = v.tid;
+            if constexpr (kTid) {
+                // `tid`: every lane its own four records when the contig changes somewhere in the sub-tile (uniform: a
+                // ballot of the run nibbles, here an iteration ahead like the mate nibble), else the block's first sector
+                // like the idle lanes of the other candidate columns.  A plain load, as theirs.
+                const bool run = __ballot((v.bits >> 4) != 0u) != 0ull;
+                const uint32_t lt = run ? (uint32_t)st * (uint32_t)(kFwSub / 4) + (uint32_t)lane : 0u;
+                c.tid = reinterpret_cast<const int4*>(b_tid)[lt];
+            }
             return c;
         };
         constexpr int kSubs = kClsTile / kFwSub;
@@ -1049,6 +1069,9 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         Round pend;                                          // the round whose rows are in flight (cnt == 0: none)
         pend.cnt = 0; pend.tid = pend.mtid = -1; pend.pos = pend.mpos = 0; pend.fm = pend.qlen = 0;
         pend.c1 = a.table[0]; pend.c2 = pend.c1;
+        // (kTid: the contig of the record before the sub-tile, uniform.  No run bit on the block's first record: it lies on
+        // the contig of the block's first record itself.)
+        int32_t cur_tid = kTid ? __builtin_amdgcn_readfirstlane(b_tid[0]) : 0;
         for (int st = 0; st < kSubs; ++st) {
             // everything issued at the top of the iteration before - it had that iteration's arithmetic to arrive - is
             // waited for here, once
@@ -1060,12 +1083,21 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
             const ColsA a2 = load_a(st2);
             pend = round_fetch(q_count >= 64 ? 64 : 0);      // (fewer than 64 are left queued: the ring holds the 256 to come)
             {
-                const int32_t r_tid[4] = {a0.tid.x, a0.tid.y, a0.tid.z, a0.tid.w};
+                // (kTid: no run bit in the sub-tile - every record lies on the contig of the one before it, cur_tid.
+                // process() is not told: it finds the 256 equal with four compares as before.  Handing it the flag to
+                // skip them made the compiler keep 96 scalars in vector lanes, not 71 - 495 lane reads in the kernel text, not
+                // 187 - and the kernel 5 % slower on full C3.)
+                const bool one_tid = kTid && __ballot((a0.bits >> 4) != 0u) == 0ull;
+                const int4 t0 = kTid ? c0.tid : a0.tid;
+                const int32_t r_tid[4] = {one_tid ? cur_tid : t0.x, one_tid ? cur_tid : t0.y, one_tid ? cur_tid : t0.z,
+                                          one_tid ? cur_tid : t0.w};
+                if (kTid && !one_tid) cur_tid = __builtin_amdgcn_readlane(t0.w, 63);
                 // (kBits: a lane that holds a candidate has read the `mtid` of its four records with the candidate columns; for
                 // a lane that holds none they equal `tid`)
-                const bool own = kBits && a0.bits != 0u;
-                const int32_t r_mtid[4] = {own ? c0.mtid.x : a0.mtid.x, own ? c0.mtid.y : a0.mtid.y, own ? c0.mtid.z : a0.mtid.z,
-                                           own ? c0.mtid.w : a0.mtid.w};
+                const bool own = kBits && (a0.bits & 15u) != 0u;
+                const int4 m0 = kBits ? make_int4(r_tid[0], r_tid[1], r_tid[2], r_tid[3]) : a0.mtid;
+                const int32_t r_mtid[4] = {own ? c0.mtid.x : m0.x, own ? c0.mtid.y : m0.y, own ? c0.mtid.z : m0.z,
+                                           own ? c0.mtid.w : m0.w};
                 const int32_t r_pos[4] = {c0.pos.x, c0.pos.y, c0.pos.z, c0.pos.w};
                 const int32_t r_mpos[4] = {c0.mpos.x, c0.mpos.y, c0.mpos.z, c0.mpos.w};
                 const uint32_t r_flag[4] = {c0.flag.x & 0xffffu, c0.flag.x >> 16, c0.flag.y & 0xffffu, c0.flag.y >> 16};
@@ -1702,14 +1734,19 @@ int launch_classify_scan(hipStream_t s, const ClassifyArgs& a, int64_t* aligned,
         if (group_runs) BESST_HIP_TRY(hipMemsetAsync(w.run_status, 0, 4, s));
         ProfScope ps(s, kProfFusedWave);
         auto* al = reinterpret_cast<unsigned long long*>(aligned);
-        if (group_runs && a.mate_bits)
-            hipLaunchKernelGGL((fused_wave_kernel<true, true>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+        // (the run bits are only honoured together with the mate bits)
+        if (group_runs && a.mate_bits && a.tid_bits)
+            hipLaunchKernelGGL((fused_wave_kernel<true, 2>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+        else if (a.mate_bits && a.tid_bits)
+            hipLaunchKernelGGL((fused_wave_kernel<false, 2>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+        else if (group_runs && a.mate_bits)
+            hipLaunchKernelGGL((fused_wave_kernel<true, 1>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
         else if (group_runs)
-            hipLaunchKernelGGL((fused_wave_kernel<true, false>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+            hipLaunchKernelGGL((fused_wave_kernel<true, 0>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
         else if (a.mate_bits)
-            hipLaunchKernelGGL((fused_wave_kernel<false, true>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+            hipLaunchKernelGGL((fused_wave_kernel<false, 1>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
         else
-            hipLaunchKernelGGL((fused_wave_kernel<false, false>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+            hipLaunchKernelGGL((fused_wave_kernel<false, 0>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
         BESST_HIP_TRY(hipGetLastError());
         return BESST_OK;
     }
@@ -1733,32 +1770,44 @@ int launch_classify_scan(hipStream_t s, const ClassifyArgs& a, int64_t* aligned,
 }
 
 namespace {
-// one thread per byte of the bit column: eight records' tid != mtid (records behind n: 0)
+// one thread per byte of the bit columns: eight records' tid != mtid and, where tid_bits is given, eight records'
+// "tid differs from the record before" (record 0: set; records behind n: 0) - one pass over `tid` for both
 __global__ __launch_bounds__(256) void mate_bits_kernel(const int32_t* __restrict__ tid, const int32_t* __restrict__ mtid,
-                                                        int64_t first_byte, int64_t n_bytes, int64_t n, uint8_t* __restrict__ bits) {
+                                                        int64_t first_byte, int64_t n_bytes, int64_t n, uint8_t* __restrict__ bits,
+                                                        uint8_t* __restrict__ tid_bits) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n_bytes) return;
     const int64_t i0 = (first_byte + k) * 8;
-    uint32_t b = 0;
+    uint32_t b = 0, r = i0 > 0 ? 0u : 1u;
+    // (the record before the byte's first is resident whenever the byte is not the stream's first)
+    int32_t prev = tid_bits && i0 > 0 ? tid[i0 - 1] : 0;
     if (i0 + 8 <= n) {
         const int4 t0 = *reinterpret_cast<const int4*>(tid + i0), t1 = *reinterpret_cast<const int4*>(tid + i0 + 4);
         const int4 m0 = *reinterpret_cast<const int4*>(mtid + i0), m1 = *reinterpret_cast<const int4*>(mtid + i0 + 4);
         b = (t0.x != m0.x ? 1u : 0u) | (t0.y != m0.y ? 2u : 0u) | (t0.z != m0.z ? 4u : 0u) | (t0.w != m0.w ? 8u : 0u) |
             (t1.x != m1.x ? 16u : 0u) | (t1.y != m1.y ? 32u : 0u) | (t1.z != m1.z ? 64u : 0u) | (t1.w != m1.w ? 128u : 0u);
+        r |= (t0.x != prev ? 1u : 0u) | (t0.y != t0.x ? 2u : 0u) | (t0.z != t0.y ? 4u : 0u) | (t0.w != t0.z ? 8u : 0u) |
+             (t1.x != t0.w ? 16u : 0u) | (t1.y != t1.x ? 32u : 0u) | (t1.z != t1.y ? 64u : 0u) | (t1.w != t1.z ? 128u : 0u);
     } else {
-        for (int j = 0; j < 8; ++j)
-            if (i0 + j < n && tid[i0 + j] != mtid[i0 + j]) b |= 1u << j;
+        for (int j = 0; j < 8 && i0 + j < n; ++j) {
+            const int32_t t = tid[i0 + j];
+            if (t != mtid[i0 + j]) b |= 1u << j;
+            if (t != prev) r |= 1u << j;
+            prev = t;
+        }
     }
+    if (tid_bits) tid_bits[first_byte + k] = (uint8_t)r;
     bits[first_byte + k] = (uint8_t)b;
 }
 }  // namespace
 
-int launch_mate_bits(hipStream_t s, const int32_t* tid, const int32_t* mtid, int64_t lo, int64_t hi, int64_t n, uint8_t* bits) {
+int launch_mate_bits(hipStream_t s, const int32_t* tid, const int32_t* mtid, int64_t lo, int64_t hi, int64_t n, uint8_t* bits,
+                     uint8_t* tid_bits) {
     if (hi > n) hi = n;
     if (lo < 0) lo = 0;
     if (hi <= lo) return BESST_OK;
     const int64_t first_byte = lo >> 3, n_bytes = ((hi + 7) >> 3) - first_byte;
-    hipLaunchKernelGGL(mate_bits_kernel, dim3((uint32_t)((n_bytes + 255) / 256)), dim3(256), 0, s, tid, mtid, first_byte, n_bytes, n, bits);
+    hipLaunchKernelGGL(mate_bits_kernel, dim3((uint32_t)((n_bytes + 255) / 256)), dim3(256), 0, s, tid, mtid, first_byte, n_bytes, n, bits, tid_bits);
     BESST_HIP_TRY(hipGetLastError());
     return BESST_OK;
 }

@@ -181,6 +181,10 @@ struct ClassifyArgs {
     uint32_t* ps_table;
     int32_t ps_rows, ps_shift;
     uint64_t ps_base;
+    // one bit per record, packed like mate_bits: record i lies on another reference than record i - 1 (record 0: set).
+    // Made in the same pass (besst_dev_record_bits); with it and mate_bits the fused loop reads `tid` only in the sub-tiles
+    // that hold such a record.  nullptr, or mate_bits nullptr: the loop reads `tid` of every record.
+    const uint8_t* tid_bits;
 };
 
 // ---- sort / reduce geometry -------------------------------------------------------------------------
@@ -338,7 +342,8 @@ int launch_candidate_density(hipStream_t s, int64_t n, const int32_t* tid, const
                              unsigned long long* counts);
 // bits of records [lo, hi) (whole bytes: from lo rounded down to hi rounded up to a multiple of 8, clipped to n: the records in
 // front of lo that share lo's byte are read again)
-int launch_mate_bits(hipStream_t s, const int32_t* tid, const int32_t* mtid, int64_t lo, int64_t hi, int64_t n, uint8_t* bits);
+int launch_mate_bits(hipStream_t s, const int32_t* tid, const int32_t* mtid, int64_t lo, int64_t hi, int64_t n, uint8_t* bits,
+                     uint8_t* tid_bits);   // (tid_bits: the run plane, written in the same pass, or nullptr)
 int launch_classify_tail(hipStream_t s, int64_t n, int32_t* tail, void* ws, size_t ws_bytes);
 int launch_resolve_carry(hipStream_t s, const int32_t* tails, int rank, int32_t* carry);
 int launch_classify_emit(hipStream_t s, int64_t n, int detect_dup, int32_t* carry, uint64_t* keys,

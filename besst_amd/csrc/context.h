@@ -54,6 +54,8 @@ struct besst_ctx {
     besst::DevBuf<uint8_t> mapq;
     besst::DevBuf<uint8_t> mate_bits;       // one bit per record: tid != mtid (ClassifyArgs::mate_bits), valid for the first bits_upto records
     int64_t bits_upto = 0;
+    besst::DevBuf<uint8_t> tid_bits;        // one bit per record: tid differs from the record before (ClassifyArgs::tid_bits), valid for the first tid_bits_upto records
+    int64_t tid_bits_upto = 0;
     // tuple stream + edge table
     besst::DevBuf<uint64_t> keys, payload, row_key;
     besst::DevBuf<uint32_t> row_mask, row_n, row_first, row_offset;

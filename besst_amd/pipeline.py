@@ -63,20 +63,34 @@ class DeviceRecords(object):
         """The ninth column of the resident layout: one bit per record, set where the mate lies on another reference
         (tid != mtid) - made once, here, when the records become resident (besst_dev_mate_bits; 1/8 byte per record).  The
         record loop then reads `mtid` only where a lane holds such a record (besst_lib_params.mate_bits).
-        BESST_MATE_BITS=0: no bit column, the loop compares tid and mtid itself (tests compare the two forms)."""
+        BESST_MATE_BITS=0: no bit column, the loop compares tid and mtid itself (tests compare the two forms).
+        The tenth column, made in the same pass (besst_dev_record_bits): one bit per record, set where the record lies on
+        another reference than the record before it.  The fused loop then reads `tid` only in the sub-tiles where it
+        changes (besst_lib_params.tid_bits).  BESST_TID_BITS=0: the mate bits alone."""
         self.mate_bits = None
+        self.tid_bits = None
         if self.n == 0 or not self.tid.is_cuda or os.environ.get('BESST_MATE_BITS') == '0':
             return
         lib = _lib.load()
         dev = self.tid.device
         bits = torch.empty(int(lib.besst_dev_mate_bits_bytes(self.n)), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.besst_dev_mate_bits(C.c_void_p(stream), self.n, _p(self.tid), _p(self.mtid), _p(bits)), 'dev_mate_bits')
+        if os.environ.get('BESST_TID_BITS') == '0':
+            _lib.check(lib.besst_dev_mate_bits(C.c_void_p(stream), self.n, _p(self.tid), _p(self.mtid), _p(bits)), 'dev_mate_bits')
+        else:
+            runs = torch.empty_like(bits)
+            _lib.check(lib.besst_dev_record_bits(C.c_void_p(stream), self.n, _p(self.tid), _p(self.mtid), _p(bits), _p(runs)),
+                       'dev_record_bits')
+            self.tid_bits = runs
         self.mate_bits = bits
 
     @property
     def mate_bits_ptr(self):
         return None if self.mate_bits is None else self.mate_bits.data_ptr()
+
+    @property
+    def tid_bits_ptr(self):
+        return None if self.tid_bits is None else self.tid_bits.data_ptr()
 
     @property
     def graph_bytes(self):
@@ -211,6 +225,7 @@ class DeviceGraphBuilder(object):
         self._last_rec = weakref.ref(rec)
         self.params.record_path = self.record_path(rec)
         self.params.mate_bits = rec.mate_bits_ptr            # (the struct the marshalled argument lists point to)
+        self.params.tid_bits = getattr(rec, 'tid_bits_ptr', None)
         # argument lists are marshalled once per record set (every buffer is allocated once)
         args = self._rec_args.get(rec)
         if args is None:

@@ -42,7 +42,8 @@ extern "C" {
  * besst_dev_text_workspace_bytes / besst_dev_text_measure / besst_dev_text_emit / besst_dev_wrap_fasta,
  * besst_dev_bgzf_deflate_bound / besst_dev_bgzf_deflate_workspace_bytes / besst_dev_bgzf_deflate / besst_bgzf_deflate_device;
  * the inflate of a BGZF file in device memory besst_bgzf_walk / besst_bgzf_scan_chunk /
- * besst_dev_bgzf_inflate_workspace_bytes / besst_dev_bgzf_inflate. */
+ * besst_dev_bgzf_inflate_workspace_bytes / besst_dev_bgzf_inflate; the run bits of the record layout besst_dev_record_bits
+ * with the trailing member besst_lib_params.tid_bits (see there). */
 #define BESST_ABI_VERSION 3
 
 /* status codes */
@@ -93,6 +94,14 @@ typedef struct besst_lib_params {
                                 * only for the lanes that hold such a record (CreateGraph.py:141-169: everything but the
                                 * coverage sum asks for contig1 != contig2).  NULL: the loop compares the columns itself.
                                 * (ABI version 3: the struct grew by this member.)                                 */
+    const void* tid_bits;      /* besst_dev_* layer: one bit per record, same packing - set iff i == 0 or tid[i] != tid[i-1] -,
+                                * made with mate_bits by besst_dev_record_bits.  The fused loop (record_path 1) then reads
+                                * `tid` only in the 256-record sub-tiles that hold such a record: in a coordinate-sorted
+                                * stream a contig's records are one run.  Only honoured together with mate_bits; NULL: the
+                                * loop reads `tid` of every record.  (The struct grew by this trailing member and
+                                * BESST_ABI_VERSION stays 3: a caller that zero-fills the struct it passes - every binding
+                                * here does - gets NULL, the earlier behaviour; a caller compiled against the shorter
+                                * struct must recompile, as at 2 -> 3.)                                           */
 } besst_lib_params;
 
 /* Tallies of the record loop: Parameter.counters (Parameter.py:113-124) plus the fishy-read count
@@ -627,6 +636,11 @@ int besst_dev_score_edges(void* stream, int64_t n_edges, const uint32_t* row, co
  * bytes.  Passed to the record loop in besst_lib_params.mate_bits. */
 size_t besst_dev_mate_bits_bytes(int64_t n_records);
 int besst_dev_mate_bits(void* stream, int64_t n_records, const int32_t* tid, const int32_t* mtid, void* bits);
+/* Both bit columns of the layout in the one pass over `tid` and `mtid`: mate_bits as above, and the run bits
+ * tid_bits[i / 8] bit i % 8 = (i == 0 || tid[i] != tid[i - 1]), same size (besst_dev_mate_bits_bytes), bits behind the last
+ * record 0.  Passed to the record loop in besst_lib_params.mate_bits / .tid_bits. */
+int besst_dev_record_bits(void* stream, int64_t n_records, const int32_t* tid, const int32_t* mtid, void* mate_bits,
+                          void* tid_bits);
 
 /* The log-normal branch on caller-owned device buffers (device-pointer forms of besst_ctx_score_edges_lognormal and
  * besst_ctx_conditional_stddevs).
