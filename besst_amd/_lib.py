@@ -37,7 +37,13 @@ class LibParams(C.Structure):
     _fields_ = [('read_len', C.c_double), ('ins_size_threshold', C.c_double), ('min_mapq', C.c_int32),
                 ('orientation', C.c_int32), ('detect_duplicate', C.c_int32), ('extend_paths', C.c_int32),
                 ('no_score', C.c_int32), ('record_path', C.c_int32), ('mate_bits', C.c_void_p),
-                ('tid_bits', C.c_void_p)]
+                ('tid_bits', C.c_void_p), ('cand_stream', C.c_void_p)]
+
+
+class CandStream(C.Structure):       # include/besst_amd.h: besst_cand_stream
+    _fields_ = [('n_refs', C.c_int64), ('n_records', C.c_int64), ('n_entries', C.c_int64), ('offsets', C.c_void_p),
+                ('set_bits', C.c_void_p), ('tid', C.c_void_p), ('mtid', C.c_void_p), ('pos', C.c_void_p),
+                ('mpos', C.c_void_p), ('flag_qlen', C.c_void_p), ('mapq', C.c_void_p)]
 
 
 class Presort(C.Structure):          # include/besst_amd.h: besst_presort
@@ -196,6 +202,12 @@ _SIGNATURES = {
     'besst_dev_mate_bits_bytes': (C.c_size_t, [C.c_int64]),
     'besst_dev_mate_bits': (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     'besst_dev_record_bits': (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    'besst_dev_candidate_offsets_bytes': (C.c_size_t, [C.c_int64]),
+    'besst_dev_candidate_stream_bytes': (C.c_size_t, [C.c_int64]),
+    'besst_dev_candidate_offsets': (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    'besst_dev_candidate_stream': (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P,
+                                             C.c_size_t, C.POINTER(CandStream)]),
+    'besst_dev_record_loop_form': (C.c_int, []),
     'besst_dev_lognormal_tables_workspace_bytes': (C.c_size_t, [C.c_int64]),
     'besst_dev_lognormal_tables': (C.c_int, [_P, C.c_double, C.c_double, C.c_int64, _P, _P, _P, C.c_size_t]),
     'besst_dev_score_edges_lognormal': (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_double,

@@ -173,6 +173,7 @@ void besst_ctx_destroy(besst_ctx* c) {
     c->table.release(); c->aligned.release();
     c->tid.release(); c->mtid.release(); c->pos.release(); c->mpos.release(); c->tlen.release();
     c->flag.release(); c->qlen.release(); c->mapq.release(); c->mate_bits.release(); c->tid_bits.release();
+    c->cs_set.release(); c->cs_off.release(); c->cs_entries.release();
     c->keys.release(); c->payload.release(); c->row_key.release();
     c->row_mask.release(); c->row_n.release(); c->row_first.release(); c->row_offset.release();
     c->row_sum.release(); c->row_sum_sq.release(); c->obs_lo.release(); c->obs_hi.release();
@@ -265,6 +266,7 @@ int besst_ctx_clear_records(besst_ctx* c) {
     c->n_records = 0;
     c->bits_upto = 0;
     c->tid_bits_upto = 0;
+    c->cs_upto = 0;
     c->built = false;
     return BESST_OK;
 }
@@ -429,6 +431,22 @@ static int fill_classify_args(ClassifyArgs& a, int64_t n, const int32_t* tid, co
     a.mate_bits = static_cast<const uint8_t*>(p->mate_bits);
     a.tid_bits = p->mate_bits ? static_cast<const uint8_t*>(p->tid_bits) : nullptr;   // (only honoured together)
     a.ps_table = nullptr; a.ps_rows = 0; a.ps_shift = 0; a.ps_base = 0;
+    // the candidate side stream: only with both bit planes, only when made for this header and these records
+    // (BESST_CAND_STREAM=0: never - A/B runs, tests)
+    a.cs_off = nullptr; a.cs_set = nullptr; a.cs_tid = a.cs_mtid = a.cs_pos = a.cs_mpos = nullptr; a.cs_fq = nullptr; a.cs_mapq = nullptr;
+    const char* cs_env = getenv("BESST_CAND_STREAM");
+    const bool cs_knob = !(cs_env && cs_env[0] == '0' && cs_env[1] == 0);
+    if (const besst_cand_stream* cs = p->cand_stream; cs && cs_knob && a.mate_bits && a.tid_bits && cs->n_refs == n_contigs &&
+                                                      cs->n_records == n && n > 0) {
+        BESST_REQUIRE(cs->offsets && cs->set_bits && cs->tid && cs->mtid && cs->pos && cs->mpos && cs->flag_qlen && cs->mapq,
+                      "classify: candidate stream with a null member");
+        a.cs_off = static_cast<const uint32_t*>(cs->offsets);
+        a.cs_set = static_cast<const uint8_t*>(cs->set_bits);
+        a.cs_tid = static_cast<const int32_t*>(cs->tid); a.cs_mtid = static_cast<const int32_t*>(cs->mtid);
+        a.cs_pos = static_cast<const int32_t*>(cs->pos); a.cs_mpos = static_cast<const int32_t*>(cs->mpos);
+        a.cs_fq = static_cast<const uint32_t*>(cs->flag_qlen);
+        a.cs_mapq = static_cast<const uint8_t*>(cs->mapq);
+    }
     BESST_REQUIRE(p->record_path == 0 || p->record_path == 1, "classify: record_path must be 0 or 1");
     return BESST_OK;
 }
@@ -684,6 +702,52 @@ int besst_dev_record_bits(void* stream, int64_t n, const int32_t* tid, const int
                             static_cast<uint8_t*>(tid_bits));
 }
 
+// ---- the candidate side stream: entries per column rounded up past n_entries (the loop's idle lanes read one more)
+static size_t cand_stream_cap(int64_t n_entries) { return align_up((size_t)(n_entries > 0 ? n_entries : 0) + 1, 64); }
+
+size_t besst_dev_candidate_offsets_bytes(int64_t n_records) {
+    const int64_t n = n_records > 0 ? n_records : 0;
+    return align_up((size_t)((n + kClsTile - 1) / kClsTile + 1) * sizeof(uint32_t), 16);
+}
+
+size_t besst_dev_candidate_stream_bytes(int64_t n_entries) { return cand_stream_cap(n_entries) * 21; }
+
+int besst_dev_candidate_offsets(void* stream, int64_t n, int64_t n_refs, const int32_t* tid, const int32_t* mtid,
+                                const uint16_t* flag, void* set_bits, void* offsets, void* mate_bits, void* tid_bits) {
+    BESST_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), "dev_candidate_offsets: record count out of range");
+    BESST_REQUIRE(n_refs >= 0, "dev_candidate_offsets: negative reference count");
+    BESST_REQUIRE(offsets && (n == 0 || (tid && mtid && flag && set_bits)), "dev_candidate_offsets: null pointer");
+    BESST_REQUIRE((mate_bits == nullptr) == (tid_bits == nullptr), "dev_candidate_offsets: both bit planes or neither");
+    BESST_REQUIRE(aligned16(tid) && aligned16(mtid) && aligned16(flag) && aligned16(set_bits),
+                  "dev_candidate_offsets: columns and the set plane must be 16-byte aligned");
+    return launch_cand_offsets(static_cast<hipStream_t>(stream), n, n_refs, tid, mtid, flag, static_cast<uint8_t*>(set_bits),
+                               static_cast<uint32_t*>(offsets), static_cast<uint8_t*>(mate_bits), static_cast<uint8_t*>(tid_bits));
+}
+
+int besst_dev_candidate_stream(void* stream, int64_t n, int64_t n_refs, const int32_t* tid, const int32_t* mtid,
+                               const int32_t* pos, const int32_t* mpos, const uint16_t* flag, const uint8_t* mapq,
+                               const uint16_t* qlen, const void* set_bits, const void* offsets, int64_t n_entries,
+                               void* entries, size_t entries_bytes, besst_cand_stream* out) {
+    BESST_REQUIRE(out, "dev_candidate_stream: null descriptor");
+    BESST_REQUIRE(n >= 0 && n < ((int64_t)1 << 32) && n_entries >= 0 && n_entries <= n, "dev_candidate_stream: counts out of range");
+    BESST_REQUIRE(offsets && entries && (n == 0 || (tid && mtid && pos && mpos && flag && mapq && qlen && set_bits)),
+                  "dev_candidate_stream: null pointer");
+    BESST_REQUIRE(aligned16(set_bits) && aligned16(entries), "dev_candidate_stream: the set plane and the entries must be 16-byte aligned");
+    BESST_REQUIRE(entries_bytes >= besst_dev_candidate_stream_bytes(n_entries), "dev_candidate_stream: entry buffer too small");
+    const size_t cap = cand_stream_cap(n_entries);
+    char* p = static_cast<char*>(entries);
+    auto* e_tid = reinterpret_cast<int32_t*>(p), *e_mtid = reinterpret_cast<int32_t*>(p + cap * 4);
+    auto* e_pos = reinterpret_cast<int32_t*>(p + cap * 8), *e_mpos = reinterpret_cast<int32_t*>(p + cap * 12);
+    auto* e_fq = reinterpret_cast<uint32_t*>(p + cap * 16);
+    auto* e_mapq = reinterpret_cast<uint8_t*>(p + cap * 20);
+    *out = besst_cand_stream{n_refs, n, n_entries, offsets, set_bits, e_tid, e_mtid, e_pos, e_mpos, e_fq, e_mapq};
+    return launch_cand_entries(static_cast<hipStream_t>(stream), n, tid, mtid, pos, mpos, flag, mapq, qlen,
+                               static_cast<const uint8_t*>(set_bits), static_cast<const uint32_t*>(offsets), e_tid, e_mtid,
+                               e_pos, e_mpos, e_fq, e_mapq, (uint32_t)(cap > 0xffffffffull ? 0xffffffffull : cap));
+}
+
+int besst_dev_record_loop_form(void) { return classify_last_form(); }
+
 size_t besst_dev_lognormal_tables_workspace_bytes(int64_t x_max) { return lognormal_tables_workspace_bytes(x_max); }
 
 int besst_dev_lognormal_tables(void* stream, double mu, double sigma, int64_t x_max, double* F0, double* F1, void* workspace,
@@ -763,6 +827,7 @@ int besst_ctx_build_graph(besst_ctx* c) {
         const char* tid_off = getenv("BESST_TID_BITS");
         lp.mate_bits = nullptr;
         lp.tid_bits = nullptr;
+        lp.cand_stream = nullptr;                            // (a stream describes the caller's columns, never the context's own)
         if (!(off && off[0] == '0' && off[1] == 0) && n > 0) {
             const bool runs = !(tid_off && tid_off[0] == '0' && tid_off[1] == 0);
             const size_t need = (size_t)((n + 7) / 8) + 16;
@@ -785,6 +850,55 @@ int besst_ctx_build_graph(besst_ctx* c) {
             }
             lp.mate_bits = c->mate_bits.p;
             if (runs) lp.tid_bits = c->tid_bits.p;
+            // The candidate side stream (fused loop only), extended like the planes for what was pushed since the last
+            // build: the block that was the stream's last then - a push may have ended inside it - is counted and written
+            // again whole, its entries go on where that block's began.  A buffer that has to grow drops what was there,
+            // and so does a contig table of another size (the set rule reads n_refs).  BESST_CAND_STREAM=0: no stream.
+            const char* cs_off_env = getenv("BESST_CAND_STREAM");
+            if (runs && lp.record_path == 1 && !(cs_off_env && cs_off_env[0] == '0' && cs_off_env[1] == 0)) {
+                if (c->cs.n_refs != c->n_contigs) c->cs_upto = 0;
+                const size_t off_words = besst_dev_candidate_offsets_bytes(n) / sizeof(uint32_t);
+                if (need > c->cs_set.cap) {
+                    if ((rc = c->cs_set.ensure(need + need / 2))) return rc;
+                    c->cs_upto = 0;
+                }
+                if (off_words > c->cs_off.cap) {
+                    if ((rc = c->cs_off.ensure(off_words + off_words / 2))) return rc;
+                    c->cs_upto = 0;
+                }
+                if (c->cs_upto < n) {
+                    const uint32_t nblocks = (uint32_t)((n + kClsTile - 1) / kClsTile);
+                    uint32_t first = (uint32_t)(c->cs_upto / kClsTile);
+                    if ((rc = launch_cand_offsets(c->stream, n, c->n_contigs, c->tid.p, c->mtid.p, c->flag.p, c->cs_set.p, c->cs_off.p,
+                                                  nullptr, nullptr, first)))
+                        return rc;
+                    uint32_t total = 0;
+                    BESST_HIP_TRY(hipMemcpyAsync(&total, c->cs_off.p + nblocks, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+                    BESST_HIP_TRY(hipStreamSynchronize(c->stream));
+                    // (the columns lie one behind the other at a stride the capacity sets: more entries than the buffer was
+                    // carved for move every column, so the entries are written again from the first block; the idle lanes
+                    // of the loop read one entry behind the last)
+                    if ((int64_t)total + 1 > c->cs_cap_entries) {
+                        const size_t bytes = besst_dev_candidate_stream_bytes(total);
+                        if ((rc = c->cs_entries.ensure(bytes + bytes / 2))) return rc;
+                        c->cs_cap_entries = (int64_t)(c->cs_entries.cap / 21 / 64 * 64);
+                        first = 0;
+                    }
+                    const size_t cap = (size_t)c->cs_cap_entries;
+                    char* e = reinterpret_cast<char*>(c->cs_entries.p);
+                    c->cs = besst_cand_stream{c->n_contigs, n, (int64_t)total, c->cs_off.p, c->cs_set.p, e, e + cap * 4, e + cap * 8,
+                                              e + cap * 12, e + cap * 16, e + cap * 20};
+                    if ((rc = launch_cand_entries(c->stream, n, c->tid.p, c->mtid.p, c->pos.p, c->mpos.p, c->flag.p, c->mapq.p,
+                                                  c->qlen.p, c->cs_set.p, c->cs_off.p, reinterpret_cast<int32_t*>(e),
+                                                  reinterpret_cast<int32_t*>(e + cap * 4), reinterpret_cast<int32_t*>(e + cap * 8),
+                                                  reinterpret_cast<int32_t*>(e + cap * 12), reinterpret_cast<uint32_t*>(e + cap * 16),
+                                                  reinterpret_cast<uint8_t*>(e + cap * 20), (uint32_t)cap, first)))
+                        return rc;
+                    c->cs_upto = n;
+                }
+                c->cs.n_records = n;
+                lp.cand_stream = &c->cs;
+            }
         }
     }
     rc = besst_dev_classify(c->stream, n, c->tid.p, c->mtid.p, c->pos.p, c->mpos.p, c->flag.p, c->mapq.p, c->qlen.p,

@@ -22,6 +22,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <atomic>
 #include <type_traits>
 
 #include "common.h"
@@ -703,6 +704,9 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
     int run_sum = 0;
     int q_head = 0, q_count = 0;                          // the queue of candidates not yet evaluated (uniform)
     constexpr bool kTid = kBits == 2;
+    // kBits == 3: the rounds of a full block take their records from the side stream (uniform; the stream's last block
+    // goes through process() and the ring like every other form)
+    const bool side_rounds = kBits == 3 && block_base + kClsTile <= a.n;
     // the chain's state (uniform): the last record of the block so far that reached CreateEdge, where the next tuple goes,
     // and the block's first reaching record (the one stitch_kernel resolves against the blocks before)
     int st_known = 0, st_p1 = 0, st_p2 = 0, st_emit = 0;
@@ -754,7 +758,11 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         const bool in_range = live && (uint32_t)tid < (uint32_t)a.n_contigs && (uint32_t)mtid < (uint32_t)a.n_contigs;
         const Eval e = eval_record(a, in_range, r.c1, r.c2, tid, mtid, pos, mpos, fm & 0xffffu, fm >> 16);
         // (the coverage credited with the streamed records is taken back when a contig is not in the table)
-        if (in_range && !(e.bits & EV_COV) && ((int32_t)(fm >> 16) >= a.min_mapq || (fm >> 16) == 0u))
+        // (kBits == 3, a block read from the side stream: an entry was credited on its mapq alone - also when its `mtid`
+        // is no reference of the header, which the streaming half cannot see)
+        const bool back = in_range ? !(e.bits & EV_COV)
+                                   : (side_rounds && live && (uint32_t)tid < (uint32_t)a.n_contigs);
+        if (back && ((int32_t)(fm >> 16) >= a.min_mapq || (fm >> 16) == 0u))
             cov_add(tid, 0ull - (unsigned long long)qlen);
         const bool reach = live && (e.bits & EV_REACH), fishy = live && (e.bits & EV_FISHY);
         const bool mapq0 = (e.bits & EV_MAPQ0) != 0, case_a = (e.bits & EV_CASEA) != 0;
@@ -970,7 +978,157 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         __builtin_amdgcn_wave_barrier();                     // (one wave: its LDS operations complete in order)
         q_count += total;
     };
-    if (block_base + kClsTile <= a.n) {
+    if (side_rounds) {
+        if constexpr (kBits == 3) {
+            // The third form: the streaming half reads the three nibbles, mapq and qlen (and `tid` where a run bit is set)
+            // and does the coverage and the non-unique tally of the mate-elsewhere records outside the set; the rounds
+            // read 64 consecutive entries of the side stream each - no pos / mpos / flag loads, no ballots, no ring.
+            // The two halves meet only in the coverage atomics, so a round is not tied to a sub-tile: iteration `it`
+            // finishes round it - 1 (its contig rows were issued an iteration ago), issues the rows of round `it` (its
+            // entries were issued an iteration ago) and the entries of round it + 1, with the column loads of the
+            // sub-tiles ahead - again one wait per iteration -, and a block with more rounds than sub-tiles (up to 256:
+            // every record in the set) goes on iterating without sub-tiles.
+            const int32_t* const b_tid = a.tid + block_base;
+            const int32_t* const b_mtid = a.mtid + block_base;
+            const uint8_t* const b_mapq = a.mapq + block_base;
+            const uint16_t* const b_qlen = a.qlen + block_base;
+            const uint8_t* const b_bits = a.mate_bits + (block_base >> 3);
+            const uint8_t* const b_tbits = a.tid_bits + (block_base >> 3);
+            const uint8_t* const b_sbits = a.cs_set + (block_base >> 3);
+            const uint32_t e_lo = a.cs_off[blockIdx.x];
+            const int n_ent = (int)(a.cs_off[blockIdx.x + 1] - e_lo);          // <= kClsTile
+            const int n_rounds = (n_ent + 63) >> 6;
+            struct ColsS { uint32_t mapq; uint2 qlen; uint32_t bits; };        // bits: mate nibble | run << 4 | set << 8
+            struct ColsT { int4 tid, mtid; };
+            struct Ent { int32_t tid, mtid, pos, mpos; uint32_t fq, mapq; };
+            typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+            auto load_s = [&](int st) {
+                const uint32_t li = (uint32_t)st * (uint32_t)(kFwSub / 4) + (uint32_t)lane;
+                const uint32_t sh = (li & 1u) * 4u;
+                ColsS v;
+                v.bits = (((uint32_t)b_bits[li >> 1] >> sh) & 15u) | ((((uint32_t)b_tbits[li >> 1] >> sh) & 15u) << 4) |
+                         ((((uint32_t)b_sbits[li >> 1] >> sh) & 15u) << 8);
+                v.mapq = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(b_mapq) + li);
+                const v2u q4 = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(b_qlen) + li);
+                v.qlen = make_uint2(q4.x, q4.y);
+                return v;
+            };
+            // `tid` where the contig changes inside the sub-tile, `mtid` (absent contigs only) for the lanes that hold a
+            // mate-elsewhere record outside the set; every other lane reads the block's first sector, so the loads in
+            // flight do not depend on the data
+            auto load_t = [&](int st, const ColsS& v) {
+                const uint32_t mine = (uint32_t)st * (uint32_t)(kFwSub / 4) + (uint32_t)lane;
+                const bool run = __ballot(((v.bits >> 4) & 15u) != 0u) != 0ull;
+                const bool need_m = !all_present && ((v.bits & 15u) & ~(v.bits >> 8)) != 0u;
+                ColsT c;
+                c.tid = reinterpret_cast<const int4*>(b_tid)[run ? mine : 0u];
+                c.mtid = reinterpret_cast<const int4*>(b_mtid)[need_m ? mine : 0u];
+                return c;
+            };
+            auto load_e = [&](int r) {
+                const int j = r * 64 + lane;
+                const uint32_t at = e_lo + (j < n_ent ? (uint32_t)j : 0u);     // (idle lanes: the block's first entry, or the one behind the stream's last)
+                Ent v;
+                v.tid = a.cs_tid[at]; v.mtid = a.cs_mtid[at]; v.pos = a.cs_pos[at]; v.mpos = a.cs_mpos[at];
+                v.fq = a.cs_fq[at]; v.mapq = a.cs_mapq[at];
+                return v;
+            };
+            auto rows = [&](const Ent& v, int r) {
+                Round q;
+                const int left = n_ent - r * 64;
+                q.cnt = left >= 64 ? 64 : (left > 0 ? left : 0);
+                const bool live = lane < q.cnt;
+                q.tid = live ? v.tid : -1; q.mtid = live ? v.mtid : -1;
+                q.pos = live ? v.pos : 0; q.mpos = live ? v.mpos : 0;
+                q.fm = live ? ((v.fq & 0xffffu) | (v.mapq << 16)) : 0u;
+                q.qlen = live ? (v.fq >> 16) : 0u;
+                const bool in_range = live && (uint32_t)q.tid < (uint32_t)a.n_contigs && (uint32_t)q.mtid < (uint32_t)a.n_contigs;
+                q.c1 = a.table[in_range ? q.tid : 0];
+                q.c2 = a.table[in_range ? q.mtid : 0];
+                return q;
+            };
+            // a sub-tile on one contig: the wave's running sum
+            auto credit = [&](int32_t ref, int mine) {
+                const int s = wave_sum_dpp(mine);
+                if (ref != run_tid) {
+                    if (lane == 0 && run_sum && (uint32_t)run_tid < (uint32_t)a.n_contigs)
+                        atomicAdd(&aligned[run_tid], (unsigned long long)run_sum);
+                    run_tid = ref;
+                    run_sum = 0;
+                }
+                run_sum += s;
+            };
+            constexpr int kSubs = kClsTile / kFwSub;
+            ColsS s0 = load_s(0), s1 = load_s(1);
+            ColsT t0 = load_t(0, s0);
+            Ent ent = load_e(0);
+            Round pend;
+            pend.cnt = 0; pend.tid = pend.mtid = -1; pend.pos = pend.mpos = 0; pend.fm = pend.qlen = 0;
+            pend.c1 = a.table[0]; pend.c2 = pend.c1;
+            int32_t cur_tid = __builtin_amdgcn_readfirstlane(b_tid[0]);
+            const int iters = n_rounds > kSubs ? n_rounds : kSubs;
+            for (int it = 0; it < iters; ++it) {
+                if (pend.cnt) round_finish(pend);            // uniform
+                pend = rows(ent, it);
+                const int st1 = it + 1 < kSubs ? it + 1 : kSubs - 1, st2 = it + 2 < kSubs ? it + 2 : kSubs - 1;
+                const ColsT t1 = load_t(st1, s1);
+                const ColsS s2 = load_s(st2);
+                ent = load_e(it + 1);
+                if (it < kSubs) {                            // uniform
+                    const uint32_t r_mapq[4] = {s0.mapq & 255u, (s0.mapq >> 8) & 255u, (s0.mapq >> 16) & 255u, s0.mapq >> 24};
+                    const uint32_t r_qlen[4] = {s0.qlen.x & 0xffffu, s0.qlen.x >> 16, s0.qlen.y & 0xffffu, s0.qlen.y >> 16};
+                    const bool one_tid = __ballot(((s0.bits >> 4) & 15u) != 0u) == 0ull;
+                    bool cov[4];
+                    int mine = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        cov[k] = (int32_t)r_mapq[k] >= a.min_mapq || r_mapq[k] == 0;
+                        mine += cov[k] ? (int)r_qlen[k] : 0;
+                    }
+                    int32_t r_tid[4] = {cur_tid, cur_tid, cur_tid, cur_tid};
+                    if (one_tid) {
+                        credit(cur_tid, mine);
+                    } else {
+                        r_tid[0] = t0.tid.x; r_tid[1] = t0.tid.y; r_tid[2] = t0.tid.z; r_tid[3] = t0.tid.w;
+                        cur_tid = __builtin_amdgcn_readlane(t0.tid.w, 63);
+                        const int32_t ref = __builtin_amdgcn_readfirstlane(r_tid[0]);
+                        const bool lane_uni = r_tid[0] == r_tid[1] && r_tid[0] == r_tid[2] && r_tid[0] == r_tid[3];
+                        if (__all(lane_uni && r_tid[0] == ref)) {
+                            credit(ref, mine);
+                        } else {
+                            int32_t key = (int32_t)(0x80000000u | (uint32_t)lane);
+                            int val = 0;
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                if (!(cov[k] && (uint32_t)r_tid[k] < (uint32_t)a.n_contigs)) continue;
+                                if (lane_uni) val += (int)r_qlen[k];
+                                else cov_add(r_tid[k], (unsigned long long)r_qlen[k]);
+                            }
+                            if (lane_uni) key = r_tid[0];
+                            wave_add_runs(aligned, key, val, lane);
+                        }
+                    }
+                    // the mate-elsewhere records outside the set [:166-167]: their `mtid` is a reference of the header (the
+                    // set rule's last clause), so only the classes are left to ask for - and with every contig in the
+                    // table not even those
+                    const uint32_t rest = (s0.bits & 15u) & ~(s0.bits >> 8);
+                    if (__ballot(rest != 0u) != 0ull) {      // uniform
+                        const int32_t r_mtid[4] = {t0.mtid.x, t0.mtid.y, t0.mtid.z, t0.mtid.w};
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (!((rest >> k) & 1u) || (uint32_t)r_tid[k] >= (uint32_t)a.n_contigs) continue;
+                            bool present = true;
+                            if (!all_present) present = a.cls8[r_tid[k]] != BESST_CLS_ABSENT && a.cls8[r_mtid[k]] != BESST_CLS_ABSENT;
+                            if (present) c_nonuniq_fishy += r_mapq[k] == 0 ? 1u : 0u;
+                            else if (cov[k]) cov_add(r_tid[k], 0ull - (unsigned long long)r_qlen[k]);
+                        }
+                    }
+                }
+                s0 = s1; s1 = s2; t0 = t1;
+            }
+            if (pend.cnt) round_finish(pend);
+        }
+    } else if (kBits != 3 && block_base + kClsTile <= a.n) {
         // A block that lies inside the stream (all but the last): ONE wait per sub-tile.  By the counters a wave of the
         // unpipelined loop sat in s_waitcnt for 72 % of its life - tid / mtid first, then pos / mpos / flag where they
         // are needed, then the contig rows of every evaluation round, each a memory latency with nothing of the wave's
@@ -1711,6 +1869,11 @@ __global__ void resolve_carry_kernel(const int32_t* __restrict__ tails, int rank
 
 }  // namespace
 
+namespace {
+std::atomic<int> g_last_form{-1};
+}
+int classify_last_form() { return g_last_form.load(); }
+
 bool classify_can_group_runs(const ClassifyArgs& a) {
     // BESST_LOOP_RUNS=0 (A/B runs, tests): the record loop writes keys and rg_group_kernel finds the runs
     static const int knob = [] { const char* e = getenv("BESST_LOOP_RUNS"); return e ? atoi(e) : 1; }();
@@ -1734,8 +1897,14 @@ int launch_classify_scan(hipStream_t s, const ClassifyArgs& a, int64_t* aligned,
         if (group_runs) BESST_HIP_TRY(hipMemsetAsync(w.run_status, 0, 4, s));
         ProfScope ps(s, kProfFusedWave);
         auto* al = reinterpret_cast<unsigned long long*>(aligned);
-        // (the run bits are only honoured together with the mate bits)
-        if (group_runs && a.mate_bits && a.tid_bits)
+        // (the run bits are only honoured together with the mate bits, the side stream only with both)
+        const bool side = a.cs_off && a.mate_bits && a.tid_bits;
+        g_last_form.store(side ? 3 : a.mate_bits ? (a.tid_bits ? 2 : 1) : 0);
+        if (group_runs && side)
+            hipLaunchKernelGGL((fused_wave_kernel<true, 3>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+        else if (side)
+            hipLaunchKernelGGL((fused_wave_kernel<false, 3>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+        else if (group_runs && a.mate_bits && a.tid_bits)
             hipLaunchKernelGGL((fused_wave_kernel<true, 2>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
         else if (a.mate_bits && a.tid_bits)
             hipLaunchKernelGGL((fused_wave_kernel<false, 2>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
@@ -1750,6 +1919,7 @@ int launch_classify_scan(hipStream_t s, const ClassifyArgs& a, int64_t* aligned,
         BESST_HIP_TRY(hipGetLastError());
         return BESST_OK;
     }
+    g_last_form.store(-1);
     {
         ProfScope ps(s, kProfStream);
         if (a.mate_bits)
@@ -1808,6 +1978,169 @@ int launch_mate_bits(hipStream_t s, const int32_t* tid, const int32_t* mtid, int
     if (hi <= lo) return BESST_OK;
     const int64_t first_byte = lo >> 3, n_bytes = ((hi + 7) >> 3) - first_byte;
     hipLaunchKernelGGL(mate_bits_kernel, dim3((uint32_t)((n_bytes + 255) / 256)), dim3(256), 0, s, tid, mtid, first_byte, n_bytes, n, bits, tid_bits);
+    BESST_HIP_TRY(hipGetLastError());
+    return BESST_OK;
+}
+
+// ---- the candidate side stream ------------------------------------------------------------------------
+// A compacted, record-ordered copy of the records that can reach an evaluation round (the set rule below takes no
+// library parameter), made when the records become resident.  Three launches, none of which waits for another
+// workgroup: count per block (+ the set plane and, on request, the two bit planes of mate_bits_kernel from the same
+// read), an exclusive scan of the block counts, the ordered write.
+namespace {
+static_assert(kClsTile == 16384, "the side stream's blocks are the record loop's: 2048 bytes of a bit plane, 256 words");
+
+__device__ __forceinline__ bool cand_in_set(int32_t t, int32_t m, uint32_t f, uint32_t n_refs) {
+    return t != m && (((f & kFlagRead2) && !(f & kFlagUnmapped)) || ((f & kFlagUnmapped) && (f & kFlagRead1)) || (uint32_t)m >= n_refs);
+}
+
+// one workgroup per block of kClsTile records, one thread per byte of the planes and turn (eight turns)
+__global__ __launch_bounds__(256) void cand_count_kernel(const int32_t* __restrict__ tid, const int32_t* __restrict__ mtid,
+                                                         const uint16_t* __restrict__ flag, int64_t n, uint32_t n_refs,
+                                                         uint8_t* __restrict__ set_bits, uint32_t* __restrict__ counts,
+                                                         uint8_t* __restrict__ mate_bits, uint8_t* __restrict__ tid_bits,
+                                                         uint32_t first_block) {
+    __shared__ int s_c[4];
+    const uint32_t block = first_block + blockIdx.x;
+    const int64_t n_bytes = (n + 7) >> 3;
+    int count = 0;
+    for (int turn = 0; turn < kClsTile / 8 / 256; ++turn) {
+        const int64_t k = (int64_t)block * (kClsTile / 8) + turn * 256 + threadIdx.x;
+        if (k >= n_bytes) break;
+        const int64_t i0 = k * 8;
+        uint32_t sb = 0, b = 0, r = i0 > 0 ? 0u : 1u;
+        int32_t prev = tid_bits && i0 > 0 ? tid[i0 - 1] : 0;
+        if (i0 + 8 <= n) {
+            const int4 t0 = *reinterpret_cast<const int4*>(tid + i0), t1 = *reinterpret_cast<const int4*>(tid + i0 + 4);
+            const int4 m0 = *reinterpret_cast<const int4*>(mtid + i0), m1 = *reinterpret_cast<const int4*>(mtid + i0 + 4);
+            const uint4 f4 = *reinterpret_cast<const uint4*>(flag + i0);
+            const int32_t t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+            const int32_t m[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+            const uint32_t f[8] = {f4.x & 0xffffu, f4.x >> 16, f4.y & 0xffffu, f4.y >> 16,
+                                   f4.z & 0xffffu, f4.z >> 16, f4.w & 0xffffu, f4.w >> 16};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (t[j] != m[j]) b |= 1u << j;
+                if (t[j] != (j ? t[j - 1] : prev)) r |= 1u << j;
+                if (cand_in_set(t[j], m[j], f[j], n_refs)) sb |= 1u << j;
+            }
+        } else {
+            for (int j = 0; j < 8 && i0 + j < n; ++j) {
+                const int32_t t = tid[i0 + j], m = mtid[i0 + j];
+                if (t != m) b |= 1u << j;
+                if (t != prev) r |= 1u << j;
+                if (cand_in_set(t, m, flag[i0 + j], n_refs)) sb |= 1u << j;
+                prev = t;
+            }
+        }
+        set_bits[k] = (uint8_t)sb;
+        if (mate_bits) mate_bits[k] = (uint8_t)b;
+        if (tid_bits) tid_bits[k] = (uint8_t)r;
+        count += __popc(sb);
+    }
+    count = wave_sum(count);
+    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = count;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[block + 1] = (uint32_t)(s_c[0] + s_c[1] + s_c[2] + s_c[3]);   // (summed in place by cand_scan_kernel)
+}
+
+// The counts of blocks first .. nblocks - 1, left at counts[b + 1], -> the entry offsets: counts[b + 1] = counts[first] + the
+// sum of the counts up to block b, in place; counts[first] is what an earlier pass left (first == 0: 0).  One workgroup:
+// 24 k values on C3.
+__global__ __launch_bounds__(1024) void cand_scan_kernel(uint32_t* __restrict__ counts, uint32_t first, uint32_t nblocks) {
+    __shared__ uint32_t s_w[16];
+    __shared__ uint32_t s_carry;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (threadIdx.x == 0) {
+        if (first == 0) counts[0] = 0u;
+        s_carry = first ? counts[first] : 0u;
+    }
+    __syncthreads();
+    for (uint32_t base = first; base < nblocks; base += 1024u) {
+        const uint32_t b = base + threadIdx.x;
+        const uint32_t c = b < nblocks ? counts[b + 1] : 0u;
+        // (unsigned throughout: a stream of up to 2^32 - 1 records may put more than 2^31 of them in the set)
+        uint32_t incl = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) s_w[w] = incl;
+        __syncthreads();
+        uint32_t before = s_carry;
+        for (int q = 0; q < w; ++q) before += s_w[q];
+        if (b < nblocks) counts[b + 1] = before + incl;
+        __syncthreads();
+        if (threadIdx.x == 1023) s_carry = before + incl;
+        __syncthreads();
+    }
+}
+
+// one workgroup per block, a wave per quarter of it; 64 records per step, one per lane, in record order
+__global__ __launch_bounds__(256) void cand_entries_kernel(
+    const int32_t* __restrict__ tid, const int32_t* __restrict__ mtid, const int32_t* __restrict__ pos,
+    const int32_t* __restrict__ mpos, const uint16_t* __restrict__ flag, const uint8_t* __restrict__ mapq,
+    const uint16_t* __restrict__ qlen, int64_t n, const uint8_t* __restrict__ set_bits, const uint32_t* __restrict__ offsets,
+    int32_t* __restrict__ e_tid, int32_t* __restrict__ e_mtid, int32_t* __restrict__ e_pos, int32_t* __restrict__ e_mpos,
+    uint32_t* __restrict__ e_fq, uint8_t* __restrict__ e_mapq, uint32_t cap, uint32_t first_block) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t block = first_block + blockIdx.x;
+    const int64_t base = (int64_t)block * kClsTile;
+    const unsigned long long* words = reinterpret_cast<const unsigned long long*>(set_bits) + (base >> 6);
+    int before = 0;
+    unsigned long long mine = 0ull;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t i0 = base + (int64_t)(q * 64 + lane) * 64;
+        unsigned long long v = i0 < n ? words[q * 64 + lane] : 0ull;
+        if (i0 < n && i0 + 64 > n) v &= (1ull << (int)(n - i0)) - 1ull;   // (the bytes behind the plane's last are not the maker's)
+        if (q < w) before += __popcll(v);
+        if (q == w) mine = v;
+    }
+    before = wave_sum(before);
+    const int pc = __popcll(mine);
+    const uint32_t start = offsets[block] + (uint32_t)before + (uint32_t)(wave_incl_scan(pc, lane) - pc);
+    for (int step = 0; step < 64; ++step) {
+        const unsigned long long m = __shfl(mine, step, 64);
+        const uint32_t at = __shfl(start, step, 64);
+        if (m == 0ull) continue;                               // uniform
+        const uint32_t e = at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (((m >> lane) & 1ull) && e < cap) {                 // (e < cap: offsets that are not this plane's write nothing behind the columns)
+            const int64_t i = base + (int64_t)(w * 64 + step) * 64 + lane;
+            e_tid[e] = tid[i];
+            e_mtid[e] = mtid[i];
+            e_pos[e] = pos[i];
+            e_mpos[e] = mpos[i];
+            e_fq[e] = (uint32_t)flag[i] | ((uint32_t)qlen[i] << 16);
+            e_mapq[e] = mapq[i];
+        }
+    }
+}
+}  // namespace
+
+int launch_cand_offsets(hipStream_t s, int64_t n, int64_t n_refs, const int32_t* tid, const int32_t* mtid,
+                        const uint16_t* flag, uint8_t* set_bits, uint32_t* offsets, uint8_t* mate_bits, uint8_t* tid_bits,
+                        uint32_t first_block) {
+    const uint32_t nblocks = (uint32_t)((n + kClsTile - 1) / kClsTile);
+    if (first_block > nblocks) first_block = nblocks;
+    const uint32_t refs = n_refs < 0 ? 0u : (n_refs > 0x7fffffffll ? 0x7fffffffu : (uint32_t)n_refs);
+    if (nblocks > first_block)
+        hipLaunchKernelGGL(cand_count_kernel, dim3(nblocks - first_block), dim3(256), 0, s, tid, mtid, flag, n, refs, set_bits,
+                           offsets, mate_bits, tid_bits, first_block);
+    hipLaunchKernelGGL(cand_scan_kernel, dim3(1), dim3(1024), 0, s, offsets, first_block, nblocks);
+    BESST_HIP_TRY(hipGetLastError());
+    return BESST_OK;
+}
+
+int launch_cand_entries(hipStream_t s, int64_t n, const int32_t* tid, const int32_t* mtid, const int32_t* pos,
+                        const int32_t* mpos, const uint16_t* flag, const uint8_t* mapq, const uint16_t* qlen,
+                        const uint8_t* set_bits, const uint32_t* offsets, int32_t* e_tid, int32_t* e_mtid, int32_t* e_pos,
+                        int32_t* e_mpos, uint32_t* e_fq, uint8_t* e_mapq, uint32_t cap, uint32_t first_block) {
+    const uint32_t nblocks = (uint32_t)((n + kClsTile - 1) / kClsTile);
+    if (nblocks <= first_block) return BESST_OK;
+    hipLaunchKernelGGL(cand_entries_kernel, dim3(nblocks - first_block), dim3(256), 0, s, tid, mtid, pos, mpos, flag, mapq, qlen, n, set_bits,
+                       offsets, e_tid, e_mtid, e_pos, e_mpos, e_fq, e_mapq, cap, first_block);
     BESST_HIP_TRY(hipGetLastError());
     return BESST_OK;
 }

@@ -185,6 +185,18 @@ struct ClassifyArgs {
     // Made in the same pass (besst_dev_record_bits); with it and mate_bits the fused loop reads `tid` only in the sub-tiles
     // that hold such a record.  nullptr, or mate_bits nullptr: the loop reads `tid` of every record.
     const uint8_t* tid_bits;
+    // The candidate side stream (besst_cand_stream, include/besst_amd.h), honoured with both bit planes and only when it
+    // was made for n_contigs references; cs_off == nullptr: none.  cs_set: one bit per record, packed like mate_bits -
+    // the record has an entry; cs_off[b] .. cs_off[b + 1]: the entries of the records of block b (kClsTile records), in
+    // record order; the entry columns hold at least one entry more than cs_off[nblocks] (idle lanes read one).
+    const uint32_t* cs_off;
+    const uint8_t* cs_set;
+    const int32_t* cs_tid;
+    const int32_t* cs_mtid;
+    const int32_t* cs_pos;
+    const int32_t* cs_mpos;
+    const uint32_t* cs_fq;     // flag | qlen << 16
+    const uint8_t* cs_mapq;
 };
 
 // ---- sort / reduce geometry -------------------------------------------------------------------------
@@ -344,6 +356,24 @@ int launch_candidate_density(hipStream_t s, int64_t n, const int32_t* tid, const
 // front of lo that share lo's byte are read again)
 int launch_mate_bits(hipStream_t s, const int32_t* tid, const int32_t* mtid, int64_t lo, int64_t hi, int64_t n, uint8_t* bits,
                      uint8_t* tid_bits);   // (tid_bits: the run plane, written in the same pass, or nullptr)
+// The candidate side stream (ClassifyArgs::cs_*), three launches and no waiting between workgroups.
+// launch_cand_offsets: the set plane, the entry offsets of the kClsTile-record blocks (nblocks + 1 values, the last
+// one the number of entries) and - where the pointers are given - both bit planes of launch_mate_bits from the same
+// read of `tid` / `mtid`.  launch_cand_entries: the entries, in record order, from the set plane and the offsets.
+// first_block > 0 (a stream that is extended): blocks first_block .. only; offsets[first_block] and the entries in front
+// of it are what the earlier pass left, the block that was the last one then is redone whole.
+int launch_cand_offsets(hipStream_t s, int64_t n, int64_t n_refs, const int32_t* tid, const int32_t* mtid,
+                        const uint16_t* flag, uint8_t* set_bits, uint32_t* offsets, uint8_t* mate_bits, uint8_t* tid_bits,
+                        uint32_t first_block = 0);
+int launch_cand_entries(hipStream_t s, int64_t n, const int32_t* tid, const int32_t* mtid, const int32_t* pos,
+                        const int32_t* mpos, const uint16_t* flag, const uint8_t* mapq, const uint16_t* qlen,
+                        const uint8_t* set_bits, const uint32_t* offsets, int32_t* e_tid, int32_t* e_mtid, int32_t* e_pos,
+                        int32_t* e_mpos, uint32_t* e_fq, uint8_t* e_mapq, uint32_t cap,
+                        uint32_t first_block = 0);   // (cap: entries a column holds)
+// the form of the record loop that launch_classify_scan launched last in this process: -1 none yet or record_path 0,
+// else fused_wave_kernel's kBits (0 columns, 1 mate bits, 2 run bits, 3 candidate stream).  One word per process: a test
+// hook, meaningless where two threads classify at once (include/besst_amd.h, besst_dev_record_loop_form)
+int classify_last_form();
 int launch_classify_tail(hipStream_t s, int64_t n, int32_t* tail, void* ws, size_t ws_bytes);
 int launch_resolve_carry(hipStream_t s, const int32_t* tails, int rank, int32_t* carry);
 int launch_classify_emit(hipStream_t s, int64_t n, int detect_dup, int32_t* carry, uint64_t* keys,

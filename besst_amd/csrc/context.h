@@ -56,6 +56,14 @@ struct besst_ctx {
     int64_t bits_upto = 0;
     besst::DevBuf<uint8_t> tid_bits;        // one bit per record: tid differs from the record before (ClassifyArgs::tid_bits), valid for the first tid_bits_upto records
     int64_t tid_bits_upto = 0;
+    // the candidate side stream of the resident records (besst_cand_stream; ClassifyArgs::cs_*), made for cs.n_refs
+    // references and valid for the first cs_upto records: extended at a build, from the block that held record cs_upto,
+    // for what was pushed since; made anew when a buffer has to grow or the contig count is another
+    besst::DevBuf<uint8_t> cs_set, cs_entries;
+    besst::DevBuf<uint32_t> cs_off;
+    besst_cand_stream cs{};
+    int64_t cs_upto = 0;
+    int64_t cs_cap_entries = 0;             // entries a column of cs_entries holds (the columns' stride)
     // tuple stream + edge table
     besst::DevBuf<uint64_t> keys, payload, row_key;
     besst::DevBuf<uint32_t> row_mask, row_n, row_first, row_offset;

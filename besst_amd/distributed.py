@@ -336,6 +336,8 @@ class HipBackend(object):
             g.params.record_path = g.record_path(r)          # sampled once (synchronises), before the first step
         g.params.mate_bits = getattr(r, 'mate_bits_ptr', None)
         g.params.tid_bits = getattr(r, 'tid_bits_ptr', None)
+        make = getattr(r, 'candidate_stream', None) if g.params.record_path == 1 else None
+        g.params.cand_stream = make(g.n_contigs) if make is not None else None
         self._call('classify_scan', self.lib.besst_dev_classify_scan, lambda: (
             r.n, p(r.tid), p(r.mtid), p(r.pos), p(r.mpos), p(r.flag), p(r.mapq), p(r.qlen),
             g.n_contigs, p(g.table), C.byref(g.params), g.node_bits, p(g.aligned), g._small(0), p(g.ws1),

@@ -36,7 +36,7 @@ def _from_np(arr, device):
 class DeviceRecords(object):
     """Record columns resident in HBM."""
 
-    def __init__(self, batch, device):
+    def __init__(self, batch, device, n_refs=None):
         self.n = len(batch)
         self.tid = _from_np(batch.tid, device)
         self.mtid = _from_np(batch.mtid, device)
@@ -47,34 +47,42 @@ class DeviceRecords(object):
         self.mapq = _from_np(batch.mapq, device)
         self.qlen = _from_np(batch.qlen, device)
 
-        self._make_bits()
+        self._make_bits(n_refs)
 
     @classmethod
-    def from_columns(cls, cols, copy=False):
+    def from_columns(cls, cols, copy=False, n_refs=None):
         """Columns that already live on the device (synth.simulate_library_device)."""
         self = cls.__new__(cls)
         self.n = int(cols['tid'].shape[0])
         for k in ('tid', 'mtid', 'pos', 'mpos', 'tlen', 'flag', 'mapq', 'qlen'):
             setattr(self, k, cols[k].clone() if copy else cols[k])
-        self._make_bits()
+        self._make_bits(n_refs)
         return self
 
-    def _make_bits(self):
+    def _make_bits(self, n_refs=None):
         """The ninth column of the resident layout: one bit per record, set where the mate lies on another reference
         (tid != mtid) - made once, here, when the records become resident (besst_dev_mate_bits; 1/8 byte per record).  The
         record loop then reads `mtid` only where a lane holds such a record (besst_lib_params.mate_bits).
         BESST_MATE_BITS=0: no bit column, the loop compares tid and mtid itself (tests compare the two forms).
         The tenth column, made in the same pass (besst_dev_record_bits): one bit per record, set where the record lies on
         another reference than the record before it.  The fused loop then reads `tid` only in the sub-tiles where it
-        changes (besst_lib_params.tid_bits).  BESST_TID_BITS=0: the mate bits alone."""
+        changes (besst_lib_params.tid_bits).  BESST_TID_BITS=0: the mate bits alone.
+        The eleventh column group, the candidate side stream (candidate_stream() below), is made with the bits - one
+        read of `tid` / `mtid` for all three planes - where the caller knows the header's reference count (n_refs);
+        where it does not, the graph builder asks for it on first use with its contig count."""
         self.mate_bits = None
         self.tid_bits = None
+        self._cand = None
         if self.n == 0 or not self.tid.is_cuda or os.environ.get('BESST_MATE_BITS') == '0':
             return
         lib = _lib.load()
         dev = self.tid.device
         bits = torch.empty(int(lib.besst_dev_mate_bits_bytes(self.n)), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
+        if n_refs is not None and os.environ.get('BESST_TID_BITS') != '0' and os.environ.get('BESST_CAND_STREAM') != '0':
+            self.mate_bits, self.tid_bits = bits, torch.empty_like(bits)
+            self._make_stream(int(n_refs), with_bits=True)
+            return
         if os.environ.get('BESST_TID_BITS') == '0':
             _lib.check(lib.besst_dev_mate_bits(C.c_void_p(stream), self.n, _p(self.tid), _p(self.mtid), _p(bits)), 'dev_mate_bits')
         else:
@@ -91,6 +99,41 @@ class DeviceRecords(object):
     @property
     def tid_bits_ptr(self):
         return None if self.tid_bits is None else self.tid_bits.data_ptr()
+
+    def _make_stream(self, n_refs, with_bits):
+        lib = _lib.load()
+        dev = self.tid.device
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        set_bits = torch.empty(int(lib.besst_dev_mate_bits_bytes(self.n)), dtype=torch.uint8, device=dev)
+        offsets = torch.empty(int(lib.besst_dev_candidate_offsets_bytes(self.n)) // 4, dtype=torch.int32, device=dev)
+        _lib.check(lib.besst_dev_candidate_offsets(stream, self.n, n_refs, _p(self.tid), _p(self.mtid), _p(self.flag),
+                                                   _p(set_bits), _p(offsets), _p(self.mate_bits) if with_bits else None,
+                                                   _p(self.tid_bits) if with_bits else None), 'dev_candidate_offsets')
+        nblocks = (self.n + 16383) // 16384
+        n_entries = int(offsets[nblocks].item()) & 0xffffffff       # (synchronises: once per record set)
+        entries = torch.empty(int(lib.besst_dev_candidate_stream_bytes(n_entries)), dtype=torch.uint8, device=dev)
+        desc = _lib.CandStream()
+        _lib.check(lib.besst_dev_candidate_stream(stream, self.n, n_refs, _p(self.tid), _p(self.mtid), _p(self.pos),
+                                                  _p(self.mpos), _p(self.flag), _p(self.mapq), _p(self.qlen), _p(set_bits),
+                                                  _p(offsets), n_entries, _p(entries), entries.numel(), C.byref(desc)),
+                   'dev_candidate_stream')
+        self._cand = (desc, set_bits, offsets, entries)
+
+    def candidate_stream(self, n_refs):
+        """Address of the descriptor (besst_cand_stream) of these records' candidate side stream for a header of n_refs
+        references, made on first use - three launches, one read of the columns - and kept while n_refs stays; None
+        where a bit plane is missing or with BESST_CAND_STREAM=0.  The stream is a function of the columns: whoever
+        changes a column in place calls _make_bits() again."""
+        if self.mate_bits is None or self.tid_bits is None or os.environ.get('BESST_CAND_STREAM') == '0':
+            return None
+        if self._cand is None or self._cand[0].n_refs != int(n_refs):
+            self._cand = None
+            self._make_stream(int(n_refs), with_bits=False)
+        return C.addressof(self._cand[0])
+
+    @property
+    def cand_stream_bytes(self):
+        return 0 if self._cand is None else sum(int(t.numel()) * t.element_size() for t in self._cand[1:])
 
     @property
     def graph_bytes(self):
@@ -226,6 +269,9 @@ class DeviceGraphBuilder(object):
         self.params.record_path = self.record_path(rec)
         self.params.mate_bits = rec.mate_bits_ptr            # (the struct the marshalled argument lists point to)
         self.params.tid_bits = getattr(rec, 'tid_bits_ptr', None)
+        # (the side stream serves the fused loop only; made on the first pass over a record set that takes it)
+        make = getattr(rec, 'candidate_stream', None) if self.params.record_path == 1 else None
+        self.params.cand_stream = make(self.n_contigs) if make is not None else None
         # argument lists are marshalled once per record set (every buffer is allocated once)
         args = self._rec_args.get(rec)
         if args is None:

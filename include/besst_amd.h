@@ -43,7 +43,9 @@ extern "C" {
  * besst_dev_bgzf_deflate_bound / besst_dev_bgzf_deflate_workspace_bytes / besst_dev_bgzf_deflate / besst_bgzf_deflate_device;
  * the inflate of a BGZF file in device memory besst_bgzf_walk / besst_bgzf_scan_chunk /
  * besst_dev_bgzf_inflate_workspace_bytes / besst_dev_bgzf_inflate; the run bits of the record layout besst_dev_record_bits
- * with the trailing member besst_lib_params.tid_bits (see there). */
+ * with the trailing member besst_lib_params.tid_bits (see there); the candidate side stream besst_cand_stream with
+ * besst_dev_candidate_offsets_bytes / besst_dev_candidate_stream_bytes / besst_dev_candidate_offsets /
+ * besst_dev_candidate_stream, the trailing member besst_lib_params.cand_stream, and besst_dev_record_loop_form. */
 #define BESST_ABI_VERSION 3
 
 /* status codes */
@@ -102,7 +104,42 @@ typedef struct besst_lib_params {
                                 * BESST_ABI_VERSION stays 3: a caller that zero-fills the struct it passes - every binding
                                 * here does - gets NULL, the earlier behaviour; a caller compiled against the shorter
                                 * struct must recompile, as at 2 -> 3.)                                           */
+    const struct besst_cand_stream* cand_stream;
+                               /* besst_dev_* layer: the candidate side stream of the records the call is given (see
+                                * besst_cand_stream below), made by besst_dev_candidate_offsets + besst_dev_candidate_stream.
+                                * The fused loop then reads pos / mpos / mtid / flag of no record: its evaluation rounds
+                                * read the stream's entries.  Only honoured together with mate_bits AND tid_bits, and only
+                                * when the stream's n_refs equals the call's n_contigs and its n_records the call's
+                                * n_records; otherwise, or NULL, or with BESST_CAND_STREAM=0 in the environment: the loop
+                                * runs as with the two bit planes.  (Trailing member, same rule as tid_bits.)       */
 } besst_lib_params;
+
+/* The candidate side stream: the eleventh column group of the resident record layout.  A compacted copy, in record
+ * order, of the records that can reach an evaluation round of the record loop.  Record i is in the set iff
+ *     tid[i] != mtid[i]  and  ( (flag & 0x80 and not flag & 0x4)  or  (flag & 0x4 and flag & 0x40)
+ *                               or  (uint32) mtid[i] >= n_refs )
+ * - read 2 and mapped, or the unmapped-read-1 quirk, or a mate reference outside the header (so that every
+ * mate-elsewhere record OUTSIDE the set has 0 <= mtid < n_refs).  The rule takes no library parameter; n_refs is the
+ * number of header references the stream was made for.  Everything here lies in device memory and is derived from the
+ * record columns: IT MUST BE MADE AGAIN WHEN ANY OF tid, mtid, pos, mpos, flag, mapq, qlen CHANGES.
+ *   set_bits   one bit per record, packed like mate_bits: the record is in the set; bits behind the last record 0
+ *   offsets    n_blocks + 1 values, n_blocks = ceil(n_records / 16384): block b (records 16384 b ...) owns the
+ *              entries [offsets[b], offsets[b + 1]); offsets[n_blocks] == n_entries
+ *   columns    per entry: tid, mtid, pos, mpos (int32), flag_qlen (uint32: flag | qlen << 16), mapq (uint8) - 21 bytes;
+ *              each column holds at least one entry more than n_entries (idle lanes of the loop read it) */
+typedef struct besst_cand_stream {
+    int64_t n_refs;
+    int64_t n_records;
+    int64_t n_entries;
+    const void* offsets;
+    const void* set_bits;
+    const void* tid;
+    const void* mtid;
+    const void* pos;
+    const void* mpos;
+    const void* flag_qlen;
+    const void* mapq;
+} besst_cand_stream;
 
 /* Tallies of the record loop: Parameter.counters (Parameter.py:113-124) plus the fishy-read count
  * `ctr` of CreateGraph.py:100,163 and the sizes of the emitted tuple stream. */
@@ -641,6 +678,31 @@ int besst_dev_mate_bits(void* stream, int64_t n_records, const int32_t* tid, con
  * record 0.  Passed to the record loop in besst_lib_params.mate_bits / .tid_bits. */
 int besst_dev_record_bits(void* stream, int64_t n_records, const int32_t* tid, const int32_t* mtid, void* mate_bits,
                           void* tid_bits);
+/* The candidate side stream (besst_cand_stream above), made in two calls because its size depends on the records:
+ *   1. besst_dev_candidate_offsets: the set plane (besst_dev_mate_bits_bytes(n) bytes, 16-byte aligned) and the entry
+ *      offsets (besst_dev_candidate_offsets_bytes(n) bytes); where mate_bits / tid_bits are not NULL it also writes the two
+ *      planes of besst_dev_record_bits from the same read of `tid` / `mtid` (both or neither).  Two launches: a count per
+ *      16384-record block and a scan of the counts.
+ *   2. read n_entries = offsets[n_blocks] (a device word; synchronise the stream first), allocate
+ *      besst_dev_candidate_stream_bytes(n_entries) bytes, and
+ *   3. besst_dev_candidate_stream: the ordered write of the entries into `entries` (one launch; no workgroup waits for
+ *      another in any of the three) and the host-side descriptor *out, whose column pointers lie inside `entries`.
+ * The descriptor goes to the record loop in besst_lib_params.cand_stream; it, set_bits, offsets and entries must stay
+ * alive and unchanged while it is in use. */
+size_t besst_dev_candidate_offsets_bytes(int64_t n_records);
+size_t besst_dev_candidate_stream_bytes(int64_t n_entries);
+int besst_dev_candidate_offsets(void* stream, int64_t n_records, int64_t n_refs, const int32_t* tid, const int32_t* mtid,
+                                const uint16_t* flag, void* set_bits, void* offsets, void* mate_bits, void* tid_bits);
+int besst_dev_candidate_stream(void* stream, int64_t n_records, int64_t n_refs, const int32_t* tid, const int32_t* mtid,
+                               const int32_t* pos, const int32_t* mpos, const uint16_t* flag, const uint8_t* mapq,
+                               const uint16_t* qlen, const void* set_bits, const void* offsets, int64_t n_entries,
+                               void* entries, size_t entries_bytes, besst_cand_stream* out);
+/* Which form of the record loop the last besst_dev_classify* / besst_ctx_build_graph call of this process launched:
+ * -1 none yet or record_path 0; record_path 1: 0 = it read every column, 1 = with mate_bits, 2 = with tid_bits as well,
+ * 3 = with the candidate side stream.  (Tests and tools; results do not depend on the form.)  ONE word per process,
+ * written by every call: with two contexts or streams classifying at the same time it names whichever call came last -
+ * read it only where one thread of the process classifies. */
+int besst_dev_record_loop_form(void);
 
 /* The log-normal branch on caller-owned device buffers (device-pointer forms of besst_ctx_score_edges_lognormal and
  * besst_ctx_conditional_stddevs).
