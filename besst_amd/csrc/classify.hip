@@ -603,7 +603,8 @@ __global__ __launch_bounds__(kOrdThreads, BESST_ORD_MIN_BLOCKS) void ordered_ker
 constexpr int kFwSub = 256;                              // records per sub-tile: four per lane
 constexpr int kFwRing = kFwSub + 64;                     // a sub-tile's worth of candidates + an unfinished round
 // (the loop below keeps two sub-tiles of column loads and one round of contig rows in flight: 123 VGPRs.  Forced
-// into the 96 of five waves per SIMD it spills and is 3 % slower than at four.)
+// into the 96 of five waves per SIMD it spills and is 3 % slower than at four.  The lean side-stream form, 121 VGPRs and
+// 2 KB of LDS, was tried at five as well: 0.88 - 0.92 ms on full C3 where four ran 0.85 - 0.86 in the same session.)
 #ifndef BESST_FW_MIN_WAVES
 #define BESST_FW_MIN_WAVES 4
 #endif
@@ -629,15 +630,21 @@ __device__ __forceinline__ int wave_sum_dpp(int v) {     // the sum in every lan
 // records, and the loop read every one of them to find that a sub-tile's 256 equal its first.  With the run bits a full
 // block reads the `tid` of a sub-tile only when one of its records differs from the record before it; elsewhere the
 // contig is the one the wave carries (cur_tid).  `tid` leaves the always-read columns: 4 of 7 1/8 bytes become 1/8.
-template <bool kRuns, int kBits>
+// kLean: the launch holds FULL blocks of a stream with a side stream only (kBits == 3): every block takes the side-stream
+// loop, and the ring, process(), round_fetch and the last block's element-wise loads - which served one workgroup of C3's
+// 24 415 - are not compiled, nor is the ring's 7 KB of LDS allocated.  The stream's partial last block is a launch of the
+// general form over one block; block0 is the number of the launch's first block.
+template <bool kRuns, int kBits, bool kLean = false>
 __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
     ClassifyArgs a, unsigned long long* __restrict__ aligned, uint64_t* __restrict__ seg_keys,
-    uint64_t* __restrict__ seg_payload, SummView summ, uint32_t* __restrict__ run_status) {
-    __shared__ uint32_t s_buf[5][kFwRing];                // tid, mtid, pos, mpos, flag | mapq << 16 of the queued candidates
-    __shared__ unsigned short s_qlen[kFwRing];
+    uint64_t* __restrict__ seg_payload, SummView summ, uint32_t* __restrict__ run_status, uint32_t block0) {
+    static_assert(!kLean || kBits == 3, "the lean form reads the side stream");
+    __shared__ uint32_t s_buf[kLean ? 1 : 5][kLean ? 1 : kFwRing];   // tid, mtid, pos, mpos, flag | mapq << 16 of the queued candidates
+    __shared__ unsigned short s_qlen[kLean ? 1 : kFwRing];
     __shared__ uint32_t s_ph[kRuns ? 1 : 256];            // the sort's two digit histograms, 16 bits per counter (<= 16 384 tuples)
     const int lane = threadIdx.x;
-    const int64_t block_base = (int64_t)blockIdx.x * kClsTile;
+    const uint32_t block = block0 + blockIdx.x;
+    const int64_t block_base = (int64_t)block * kClsTile;
     // (lanes below this one in a ballot: v_mbcnt_lo/hi on the mask - a (1 << lane) - 1 kept in registers for the whole
     // block cost two of the 128 a wave has at four per SIMD, and this loop spills)
     auto below_cnt = [](unsigned long long m) {
@@ -704,9 +711,9 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
     int run_sum = 0;
     int q_head = 0, q_count = 0;                          // the queue of candidates not yet evaluated (uniform)
     constexpr bool kTid = kBits == 2;
-    // kBits == 3: the rounds of a full block take their records from the side stream (uniform; the stream's last block
-    // goes through process() and the ring like every other form)
-    const bool side_rounds = kBits == 3 && block_base + kClsTile <= a.n;
+    // kBits == 3: the rounds of a full block take their records from the side stream - in the lean form, which is launched
+    // over the full blocks; the stream's last block goes through process() and the ring like every other form
+    constexpr bool side_rounds = kLean;
     // the chain's state (uniform): the last record of the block so far that reached CreateEdge, where the next tuple goes,
     // and the block's first reaching record (the one stitch_kernel resolves against the blocks before)
     int st_known = 0, st_p1 = 0, st_p2 = 0, st_emit = 0;
@@ -756,7 +763,15 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         const int32_t tid = r.tid, mtid = r.mtid, pos = r.pos, mpos = r.mpos;
         const uint32_t fm = r.fm, qlen = r.qlen;
         const bool in_range = live && (uint32_t)tid < (uint32_t)a.n_contigs && (uint32_t)mtid < (uint32_t)a.n_contigs;
-        const Eval e = eval_record(a, in_range, r.c1, r.c2, tid, mtid, pos, mpos, fm & 0xffffu, fm >> 16);
+        ContigRow c1 = r.c1, c2 = r.c2;
+        if constexpr (kLean) {
+            // (the rows are first touched HERE: left to itself the compiler moves the first arithmetic on them - a few
+            // negations the loop's copies of this block share - up to the back edge, and with it the wait for the gathers,
+            // in front of the next iteration's loads)
+            asm volatile("" : "+v"(c1.w0), "+v"(c1.scaf_len), "+v"(c1.ctg_pos), "+v"(c1.ctg_len));
+            asm volatile("" : "+v"(c2.w0), "+v"(c2.scaf_len), "+v"(c2.ctg_pos), "+v"(c2.ctg_len));
+        }
+        const Eval e = eval_record(a, in_range, c1, c2, tid, mtid, pos, mpos, fm & 0xffffu, fm >> 16);
         // (the coverage credited with the streamed records is taken back when a contig is not in the table)
         // (kBits == 3, a block read from the side stream: an entry was credited on its mapq alone - also when its `mtid`
         // is no reference of the header, which the streaming half cannot see)
@@ -978,156 +993,194 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         __builtin_amdgcn_wave_barrier();                     // (one wave: its LDS operations complete in order)
         q_count += total;
     };
-    if (side_rounds) {
-        if constexpr (kBits == 3) {
-            // The third form: the streaming half reads the three nibbles, mapq and qlen (and `tid` where a run bit is set)
-            // and does the coverage and the non-unique tally of the mate-elsewhere records outside the set; the rounds
-            // read 64 consecutive entries of the side stream each - no pos / mpos / flag loads, no ballots, no ring.
-            // The two halves meet only in the coverage atomics, so a round is not tied to a sub-tile: iteration `it`
-            // finishes round it - 1 (its contig rows were issued an iteration ago), issues the rows of round `it` (its
-            // entries were issued an iteration ago) and the entries of round it + 1, with the column loads of the
-            // sub-tiles ahead - again one wait per iteration -, and a block with more rounds than sub-tiles (up to 256:
-            // every record in the set) goes on iterating without sub-tiles.
-            const int32_t* const b_tid = a.tid + block_base;
-            const int32_t* const b_mtid = a.mtid + block_base;
-            const uint8_t* const b_mapq = a.mapq + block_base;
-            const uint16_t* const b_qlen = a.qlen + block_base;
-            const uint8_t* const b_bits = a.mate_bits + (block_base >> 3);
-            const uint8_t* const b_tbits = a.tid_bits + (block_base >> 3);
-            const uint8_t* const b_sbits = a.cs_set + (block_base >> 3);
-            const uint32_t e_lo = a.cs_off[blockIdx.x];
-            const int n_ent = (int)(a.cs_off[blockIdx.x + 1] - e_lo);          // <= kClsTile
-            const int n_rounds = (n_ent + 63) >> 6;
-            struct ColsS { uint32_t mapq; uint2 qlen; uint32_t bits; };        // bits: mate nibble | run << 4 | set << 8
-            struct ColsT { int4 tid, mtid; };
-            struct Ent { int32_t tid, mtid, pos, mpos; uint32_t fq, mapq; };
-            typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-            auto load_s = [&](int st) {
-                const uint32_t li = (uint32_t)st * (uint32_t)(kFwSub / 4) + (uint32_t)lane;
-                const uint32_t sh = (li & 1u) * 4u;
-                ColsS v;
-                v.bits = (((uint32_t)b_bits[li >> 1] >> sh) & 15u) | ((((uint32_t)b_tbits[li >> 1] >> sh) & 15u) << 4) |
-                         ((((uint32_t)b_sbits[li >> 1] >> sh) & 15u) << 8);
-                v.mapq = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(b_mapq) + li);
-                const v2u q4 = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(b_qlen) + li);
-                v.qlen = make_uint2(q4.x, q4.y);
-                return v;
-            };
-            // `tid` where the contig changes inside the sub-tile, `mtid` (absent contigs only) for the lanes that hold a
-            // mate-elsewhere record outside the set; every other lane reads the block's first sector, so the loads in
-            // flight do not depend on the data
-            auto load_t = [&](int st, const ColsS& v) {
-                const uint32_t mine = (uint32_t)st * (uint32_t)(kFwSub / 4) + (uint32_t)lane;
-                const bool run = __ballot(((v.bits >> 4) & 15u) != 0u) != 0ull;
-                const bool need_m = !all_present && ((v.bits & 15u) & ~(v.bits >> 8)) != 0u;
-                ColsT c;
-                c.tid = reinterpret_cast<const int4*>(b_tid)[run ? mine : 0u];
-                c.mtid = reinterpret_cast<const int4*>(b_mtid)[need_m ? mine : 0u];
-                return c;
-            };
-            auto load_e = [&](int r) {
-                const int j = r * 64 + lane;
-                const uint32_t at = e_lo + (j < n_ent ? (uint32_t)j : 0u);     // (idle lanes: the block's first entry, or the one behind the stream's last)
-                Ent v;
-                v.tid = a.cs_tid[at]; v.mtid = a.cs_mtid[at]; v.pos = a.cs_pos[at]; v.mpos = a.cs_mpos[at];
-                v.fq = a.cs_fq[at]; v.mapq = a.cs_mapq[at];
-                return v;
-            };
-            auto rows = [&](const Ent& v, int r) {
-                Round q;
-                const int left = n_ent - r * 64;
-                q.cnt = left >= 64 ? 64 : (left > 0 ? left : 0);
-                const bool live = lane < q.cnt;
-                q.tid = live ? v.tid : -1; q.mtid = live ? v.mtid : -1;
-                q.pos = live ? v.pos : 0; q.mpos = live ? v.mpos : 0;
-                q.fm = live ? ((v.fq & 0xffffu) | (v.mapq << 16)) : 0u;
-                q.qlen = live ? (v.fq >> 16) : 0u;
-                const bool in_range = live && (uint32_t)q.tid < (uint32_t)a.n_contigs && (uint32_t)q.mtid < (uint32_t)a.n_contigs;
-                q.c1 = a.table[in_range ? q.tid : 0];
-                q.c2 = a.table[in_range ? q.mtid : 0];
-                return q;
-            };
-            // a sub-tile on one contig: the wave's running sum
-            auto credit = [&](int32_t ref, int mine) {
-                const int s = wave_sum_dpp(mine);
-                if (ref != run_tid) {
-                    if (lane == 0 && run_sum && (uint32_t)run_tid < (uint32_t)a.n_contigs)
-                        atomicAdd(&aligned[run_tid], (unsigned long long)run_sum);
-                    run_tid = ref;
-                    run_sum = 0;
-                }
-                run_sum += s;
-            };
-            constexpr int kSubs = kClsTile / kFwSub;
-            ColsS s0 = load_s(0), s1 = load_s(1);
-            ColsT t0 = load_t(0, s0);
-            Ent ent = load_e(0);
-            Round pend;
-            pend.cnt = 0; pend.tid = pend.mtid = -1; pend.pos = pend.mpos = 0; pend.fm = pend.qlen = 0;
-            pend.c1 = a.table[0]; pend.c2 = pend.c1;
-            int32_t cur_tid = __builtin_amdgcn_readfirstlane(b_tid[0]);
-            const int iters = n_rounds > kSubs ? n_rounds : kSubs;
-            for (int it = 0; it < iters; ++it) {
-                if (pend.cnt) round_finish(pend);            // uniform
-                pend = rows(ent, it);
-                const int st1 = it + 1 < kSubs ? it + 1 : kSubs - 1, st2 = it + 2 < kSubs ? it + 2 : kSubs - 1;
-                const ColsT t1 = load_t(st1, s1);
-                const ColsS s2 = load_s(st2);
-                ent = load_e(it + 1);
-                if (it < kSubs) {                            // uniform
-                    const uint32_t r_mapq[4] = {s0.mapq & 255u, (s0.mapq >> 8) & 255u, (s0.mapq >> 16) & 255u, s0.mapq >> 24};
-                    const uint32_t r_qlen[4] = {s0.qlen.x & 0xffffu, s0.qlen.x >> 16, s0.qlen.y & 0xffffu, s0.qlen.y >> 16};
-                    const bool one_tid = __ballot(((s0.bits >> 4) & 15u) != 0u) == 0ull;
-                    bool cov[4];
-                    int mine = 0;
+    if constexpr (kLean) {
+        // The third form: the streaming half reads the three nibbles, mapq and qlen (and `tid` where a run bit is set)
+        // and does the coverage and the non-unique tally of the mate-elsewhere records outside the set; the rounds
+        // read 64 consecutive entries of the side stream each - no pos / mpos / flag loads, no ballots, no ring.
+        // The two halves meet only in the coverage atomics, so a round is not tied to a sub-tile, and a block with more
+        // rounds than sub-tiles (up to 256: every record in the set) goes on iterating without sub-tiles.
+        //
+        // A software pipeline.  Iteration `it`
+        //   1. issues the column loads of the sub-tiles ahead: `tid` / `mtid` and mapq / qlen of sub-tile it + 1 and, every
+        //      other iteration, the nibble bytes of it + 2 and it + 3;
+        //   2. finishes round it - 1, whose rows were issued before the streaming half of the iteration before: its wait
+        //      is a counted one and leaves what step 1 has just issued in flight;
+        //   3. issues the contig rows of round `it` (its entries were issued an iteration ago) and the entries of round
+        //      it + 1, behind the stores of step 2 and consumed only after the loads of the next step 1: no store round
+        //      trip stands in front of a load's use;
+        //   4. runs the streaming half on sub-tile `it`.
+        // (Before, the compiler copied the freshly loaded entries into their loop-carried registers in front of the
+        // round: an s_waitcnt vmcnt(0) ahead of the loop's largest block of arithmetic, which then ran with no load of
+        // the wave in flight.  With the rows of round `it` issued in step 1, a whole iteration ahead, two rounds are live
+        // at once: 128 VGPRs and six of them spilled, reloaded behind a vmcnt(0) inside the loop - measured slower.)  The
+        // loop is unrolled by two and the column buffers keep their registers while their role alternates: A is loaded
+        // in odd iterations and consumed in even ones, B the other way round; `pend` and `ent` are rewritten only after
+        // their last use.  No register a load of the same iteration writes is copied at the back edge - only the two
+        // nibble sets, loaded an iteration and a half before.  The nibble bytes stay as they were loaded until a
+        // sub-tile is processed (a shift at the load would wait for them on the spot).  An odd number of iterations
+        // is rounded up: the extra one is past both the sub-tiles and the rounds and goes through the same code.
+        const int32_t* const b_tid = a.tid + block_base;
+        const int32_t* const b_mtid = a.mtid + block_base;
+        const uint8_t* const b_mapq = a.mapq + block_base;
+        const uint16_t* const b_qlen = a.qlen + block_base;
+        const uint8_t* const b_bits = a.mate_bits + (block_base >> 3);
+        const uint8_t* const b_tbits = a.tid_bits + (block_base >> 3);
+        const uint8_t* const b_sbits = a.cs_set + (block_base >> 3);
+        const uint32_t e_lo = a.cs_off[block];
+        const int n_ent = (int)(a.cs_off[block + 1] - e_lo);                // <= kClsTile
+        const int n_rounds = (n_ent + 63) >> 6;
+        constexpr int kSubs = kClsTile / kFwSub;
+        struct ColsB { uint32_t mate, run, set; };                         // the bytes that hold the lane's three nibbles
+        struct ColsQ { uint32_t mapq; uint2 qlen; };
+        struct ColsT { int4 tid, mtid; };
+        struct Ent { int32_t tid, mtid, pos, mpos; uint32_t fq, mapq; };
+        typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+        // (the lane's four records begin at block_base + 4 li: their bits are a nibble of byte li / 2 of the block's, the
+        // high one in odd lanes - a sub-tile begins at an even li)
+        auto nib = [&](uint32_t byte) __attribute__((always_inline)) { return (byte >> (((uint32_t)lane & 1u) * 4u)) & 15u; };
+        auto load_b = [&](int st) __attribute__((always_inline)) {
+            st = st < kSubs ? st : kSubs - 1;
+            const uint32_t li = (uint32_t)st * (uint32_t)(kFwSub / 4) + (uint32_t)lane;
+            ColsB v;
+            v.mate = b_bits[li >> 1]; v.run = b_tbits[li >> 1]; v.set = b_sbits[li >> 1];
+            return v;
+        };
+        auto load_q = [&](int st) __attribute__((always_inline)) {
+            st = st < kSubs ? st : kSubs - 1;
+            const uint32_t li = (uint32_t)st * (uint32_t)(kFwSub / 4) + (uint32_t)lane;
+            ColsQ v;
+            v.mapq = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(b_mapq) + li);
+            const v2u q4 = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(b_qlen) + li);
+            v.qlen = make_uint2(q4.x, q4.y);
+            return v;
+        };
+        // `tid` where the contig changes inside the sub-tile, `mtid` (absent contigs only) for the lanes that hold a
+        // mate-elsewhere record outside the set; every other lane reads the block's first sector, so the loads in
+        // flight do not depend on the data
+        auto load_t = [&](int st, const ColsB& b) __attribute__((always_inline)) {
+            st = st < kSubs ? st : kSubs - 1;
+            const uint32_t mine = (uint32_t)st * (uint32_t)(kFwSub / 4) + (uint32_t)lane;
+            const bool run = __ballot(nib(b.run) != 0u) != 0ull;
+            const bool need_m = !all_present && (nib(b.mate) & ~nib(b.set)) != 0u;
+            ColsT c;
+            c.tid = reinterpret_cast<const int4*>(b_tid)[run ? mine : 0u];
+            c.mtid = reinterpret_cast<const int4*>(b_mtid)[need_m ? mine : 0u];
+            return c;
+        };
+        auto load_e = [&](int r) __attribute__((always_inline)) {
+            const int j = r * 64 + lane;
+            const uint32_t at = e_lo + (j < n_ent ? (uint32_t)j : 0u);     // (idle lanes: the block's first entry, or the one behind the stream's last)
+            Ent v;
+            v.tid = a.cs_tid[at]; v.mtid = a.cs_mtid[at]; v.pos = a.cs_pos[at]; v.mpos = a.cs_mpos[at];
+            v.fq = a.cs_fq[at]; v.mapq = a.cs_mapq[at];
+            return v;
+        };
+        auto rows = [&](const Ent& v, int r) __attribute__((always_inline)) {
+            Round q;
+            const int left = n_ent - r * 64;
+            q.cnt = left >= 64 ? 64 : (left > 0 ? left : 0);
+            const bool live = lane < q.cnt;
+            q.tid = live ? v.tid : -1; q.mtid = live ? v.mtid : -1;
+            q.pos = live ? v.pos : 0; q.mpos = live ? v.mpos : 0;
+            q.fm = live ? ((v.fq & 0xffffu) | (v.mapq << 16)) : 0u;
+            q.qlen = live ? (v.fq >> 16) : 0u;
+            const bool in_range = live && (uint32_t)q.tid < (uint32_t)a.n_contigs && (uint32_t)q.mtid < (uint32_t)a.n_contigs;
+            q.c1 = a.table[in_range ? q.tid : 0];
+            q.c2 = a.table[in_range ? q.mtid : 0];
+            return q;
+        };
+        // a sub-tile on one contig: the wave's running sum
+        auto credit = [&](int32_t ref, int mine) __attribute__((always_inline)) {
+            const int s = wave_sum_dpp(mine);
+            if (ref != run_tid) {
+                if (lane == 0 && run_sum && (uint32_t)run_tid < (uint32_t)a.n_contigs)
+                    atomicAdd(&aligned[run_tid], (unsigned long long)run_sum);
+                run_tid = ref;
+                run_sum = 0;
+            }
+            run_sum += s;
+        };
+        int32_t cur_tid = __builtin_amdgcn_readfirstlane(b_tid[0]);
+        // ---- the streaming half of one sub-tile
+        auto stream = [&](const ColsQ& q, const ColsB& b, const ColsT& t) __attribute__((always_inline)) {
+            const uint32_t n_mate = nib(b.mate), n_run = nib(b.run), n_set = nib(b.set);
+            const uint32_t r_mapq[4] = {q.mapq & 255u, (q.mapq >> 8) & 255u, (q.mapq >> 16) & 255u, q.mapq >> 24};
+            const uint32_t r_qlen[4] = {q.qlen.x & 0xffffu, q.qlen.x >> 16, q.qlen.y & 0xffffu, q.qlen.y >> 16};
+            const bool one_tid = __ballot(n_run != 0u) == 0ull;
+            bool cov[4];
+            int mine = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                cov[k] = (int32_t)r_mapq[k] >= a.min_mapq || r_mapq[k] == 0;
+                mine += cov[k] ? (int)r_qlen[k] : 0;
+            }
+            int32_t r_tid[4] = {cur_tid, cur_tid, cur_tid, cur_tid};
+            if (one_tid) {
+                credit(cur_tid, mine);
+            } else {
+                r_tid[0] = t.tid.x; r_tid[1] = t.tid.y; r_tid[2] = t.tid.z; r_tid[3] = t.tid.w;
+                cur_tid = __builtin_amdgcn_readlane(t.tid.w, 63);
+                const int32_t ref = __builtin_amdgcn_readfirstlane(r_tid[0]);
+                const bool lane_uni = r_tid[0] == r_tid[1] && r_tid[0] == r_tid[2] && r_tid[0] == r_tid[3];
+                if (__all(lane_uni && r_tid[0] == ref)) {
+                    credit(ref, mine);
+                } else {
+                    int32_t key = (int32_t)(0x80000000u | (uint32_t)lane);
+                    int val = 0;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        cov[k] = (int32_t)r_mapq[k] >= a.min_mapq || r_mapq[k] == 0;
-                        mine += cov[k] ? (int)r_qlen[k] : 0;
+                        if (!(cov[k] && (uint32_t)r_tid[k] < (uint32_t)a.n_contigs)) continue;
+                        if (lane_uni) val += (int)r_qlen[k];
+                        else cov_add(r_tid[k], (unsigned long long)r_qlen[k]);
                     }
-                    int32_t r_tid[4] = {cur_tid, cur_tid, cur_tid, cur_tid};
-                    if (one_tid) {
-                        credit(cur_tid, mine);
-                    } else {
-                        r_tid[0] = t0.tid.x; r_tid[1] = t0.tid.y; r_tid[2] = t0.tid.z; r_tid[3] = t0.tid.w;
-                        cur_tid = __builtin_amdgcn_readlane(t0.tid.w, 63);
-                        const int32_t ref = __builtin_amdgcn_readfirstlane(r_tid[0]);
-                        const bool lane_uni = r_tid[0] == r_tid[1] && r_tid[0] == r_tid[2] && r_tid[0] == r_tid[3];
-                        if (__all(lane_uni && r_tid[0] == ref)) {
-                            credit(ref, mine);
-                        } else {
-                            int32_t key = (int32_t)(0x80000000u | (uint32_t)lane);
-                            int val = 0;
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                if (!(cov[k] && (uint32_t)r_tid[k] < (uint32_t)a.n_contigs)) continue;
-                                if (lane_uni) val += (int)r_qlen[k];
-                                else cov_add(r_tid[k], (unsigned long long)r_qlen[k]);
-                            }
-                            if (lane_uni) key = r_tid[0];
-                            wave_add_runs(aligned, key, val, lane);
-                        }
-                    }
-                    // the mate-elsewhere records outside the set [:166-167]: their `mtid` is a reference of the header (the
-                    // set rule's last clause), so only the classes are left to ask for - and with every contig in the
-                    // table not even those
-                    const uint32_t rest = (s0.bits & 15u) & ~(s0.bits >> 8);
-                    if (__ballot(rest != 0u) != 0ull) {      // uniform
-                        const int32_t r_mtid[4] = {t0.mtid.x, t0.mtid.y, t0.mtid.z, t0.mtid.w};
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (!((rest >> k) & 1u) || (uint32_t)r_tid[k] >= (uint32_t)a.n_contigs) continue;
-                            bool present = true;
-                            if (!all_present) present = a.cls8[r_tid[k]] != BESST_CLS_ABSENT && a.cls8[r_mtid[k]] != BESST_CLS_ABSENT;
-                            if (present) c_nonuniq_fishy += r_mapq[k] == 0 ? 1u : 0u;
-                            else if (cov[k]) cov_add(r_tid[k], 0ull - (unsigned long long)r_qlen[k]);
-                        }
-                    }
+                    if (lane_uni) key = r_tid[0];
+                    wave_add_runs(aligned, key, val, lane);
                 }
-                s0 = s1; s1 = s2; t0 = t1;
             }
-            if (pend.cnt) round_finish(pend);
+            // the mate-elsewhere records outside the set [:166-167]: their `mtid` is a reference of the header (the
+            // set rule's last clause), so only the classes are left to ask for - and with every contig in the
+            // table not even those
+            const uint32_t rest = n_mate & ~n_set;
+            if (__ballot(rest != 0u) != 0ull) {              // uniform
+                const int32_t r_mtid[4] = {t.mtid.x, t.mtid.y, t.mtid.z, t.mtid.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (!((rest >> k) & 1u) || (uint32_t)r_tid[k] >= (uint32_t)a.n_contigs) continue;
+                    bool present = true;
+                    if (!all_present) present = a.cls8[r_tid[k]] != BESST_CLS_ABSENT && a.cls8[r_mtid[k]] != BESST_CLS_ABSENT;
+                    if (present) c_nonuniq_fishy += r_mapq[k] == 0 ? 1u : 0u;
+                    else if (cov[k]) cov_add(r_tid[k], 0ull - (unsigned long long)r_qlen[k]);
+                }
+            }
+        };
+        ColsB bA = load_b(0), bB = load_b(1), bC = bA, bD = bB;
+        ColsQ qA = load_q(0), qB = qA;
+        ColsT tA = load_t(0, bA), tB = tA;
+        Ent ent = load_e(0);
+        Round pend;                                          // the round whose rows are in flight (cnt == 0: none)
+        pend.cnt = 0; pend.tid = pend.mtid = -1; pend.pos = pend.mpos = 0; pend.fm = pend.qlen = 0;
+        pend.c1 = a.table[0]; pend.c2 = pend.c1;
+        const int iters = ((n_rounds > kSubs ? n_rounds : kSubs) + 1) & ~1;
+        for (int it = 0; it < iters; it += 2) {
+            // ---- even iteration: columns into B, sub-tile from A
+            tB = load_t(it + 1, bB);
+            qB = load_q(it + 1);
+            bC = load_b(it + 2);
+            bD = load_b(it + 3);
+            if (pend.cnt) round_finish(pend);                // uniform
+            pend = rows(ent, it);
+            ent = load_e(it + 1);
+            if (it < kSubs) stream(qA, bA, tA);              // uniform
+            // ---- odd iteration: columns into A, sub-tile from B
+            tA = load_t(it + 2, bC);
+            qA = load_q(it + 2);
+            if (pend.cnt) round_finish(pend);                // uniform
+            pend = rows(ent, it + 1);
+            ent = load_e(it + 2);
+            if (it + 1 < kSubs) stream(qB, bB, tB);          // uniform
+            bA = bC; bB = bD;
         }
+        if (pend.cnt) round_finish(pend);
     } else if (kBits != 3 && block_base + kClsTile <= a.n) {
         // A block that lies inside the stream (all but the last): ONE wait per sub-tile.  By the counters a wave of the
         // unpipelined loop sat in s_waitcnt for 72 % of its life - tid / mtid first, then pos / mpos / flag where they
@@ -1291,7 +1344,9 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
             while (q_count >= 64) run_round(64);
         }
     }
-    if (q_count > 0) run_round(q_count);                    // the unfinished round (uniform)
+    if constexpr (!kLean) {
+        if (q_count > 0) run_round(q_count);                // the unfinished round (uniform)
+    }
     if (lane == 0 && run_sum && (uint32_t)run_tid < (uint32_t)a.n_contigs)
         atomicAdd(&aligned[run_tid], (unsigned long long)run_sum);
     // ---- block summary (same planes as ordered_kernel)
@@ -1307,7 +1362,7 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
     }
     if (!kRuns && a.ps_table) {
         __builtin_amdgcn_wave_barrier();
-        uint32_t* row = a.ps_table + (size_t)(blockIdx.x & (uint32_t)(a.ps_rows - 1)) * 512u;
+        uint32_t* row = a.ps_table + (size_t)(block & (uint32_t)(a.ps_rows - 1)) * 512u;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int d = q * 64 + lane;
@@ -1331,7 +1386,7 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         if (lane == kSumChunks) v = (uint32_t)rl_chunks;
         if (lane == kSumRuns) v = (uint32_t)rl_runs + ((hd_present && hd_slot != (int)kNoSlot) ? 1u : 0u);
     }
-    if (lane < kSumPlanes) summ.at(lane, blockIdx.x) = v;
+    if (lane < kSumPlanes) summ.at(lane, block) = v;
 }
 
 // ---- stitch: resolve block heads, fix counters, scan tuple counts ------------------------------------
@@ -1900,22 +1955,30 @@ int launch_classify_scan(hipStream_t s, const ClassifyArgs& a, int64_t* aligned,
         // (the run bits are only honoured together with the mate bits, the side stream only with both)
         const bool side = a.cs_off && a.mate_bits && a.tid_bits;
         g_last_form.store(side ? 3 : a.mate_bits ? (a.tid_bits ? 2 : 1) : 0);
-        if (group_runs && side)
-            hipLaunchKernelGGL((fused_wave_kernel<true, 3>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
-        else if (side)
-            hipLaunchKernelGGL((fused_wave_kernel<false, 3>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
-        else if (group_runs && a.mate_bits && a.tid_bits)
-            hipLaunchKernelGGL((fused_wave_kernel<true, 2>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+        if (side) {
+            // the lean form over the full blocks, the general form over the stream's partial last block (both under the
+            // one scope and the one kernel name)
+            const uint32_t full = (uint32_t)(a.n / kClsTile);
+            if (full && group_runs)
+                hipLaunchKernelGGL((fused_wave_kernel<true, 3, true>), dim3(full), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, 0u);
+            else if (full)
+                hipLaunchKernelGGL((fused_wave_kernel<false, 3, true>), dim3(full), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, 0u);
+            if (full < nblocks && group_runs)
+                hipLaunchKernelGGL((fused_wave_kernel<true, 3>), dim3(nblocks - full), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, full);
+            else if (full < nblocks)
+                hipLaunchKernelGGL((fused_wave_kernel<false, 3>), dim3(nblocks - full), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, full);
+        } else if (group_runs && a.mate_bits && a.tid_bits)
+            hipLaunchKernelGGL((fused_wave_kernel<true, 2>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, 0u);
         else if (a.mate_bits && a.tid_bits)
-            hipLaunchKernelGGL((fused_wave_kernel<false, 2>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+            hipLaunchKernelGGL((fused_wave_kernel<false, 2>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, 0u);
         else if (group_runs && a.mate_bits)
-            hipLaunchKernelGGL((fused_wave_kernel<true, 1>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+            hipLaunchKernelGGL((fused_wave_kernel<true, 1>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, 0u);
         else if (group_runs)
-            hipLaunchKernelGGL((fused_wave_kernel<true, 0>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+            hipLaunchKernelGGL((fused_wave_kernel<true, 0>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, 0u);
         else if (a.mate_bits)
-            hipLaunchKernelGGL((fused_wave_kernel<false, 1>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+            hipLaunchKernelGGL((fused_wave_kernel<false, 1>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, 0u);
         else
-            hipLaunchKernelGGL((fused_wave_kernel<false, 0>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status);
+            hipLaunchKernelGGL((fused_wave_kernel<false, 0>), dim3(nblocks), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, 0u);
         BESST_HIP_TRY(hipGetLastError());
         return BESST_OK;
     }
