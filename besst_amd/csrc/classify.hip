@@ -37,6 +37,12 @@ constexpr uint32_t kNoSlot = 0xffffffffu;
 constexpr uint32_t EV_COV = 1u, EV_FISHY = 2u, EV_NONUNIQ = 4u, EV_REACH = 8u,
                    EV_DOUBLE = 32u, EV_MAPQ0 = 64u, EV_CASEA = 128u, EV_FIRSTMIN = 256u;
 
+// What the lean side-stream loop may know of a library at compile time (fused_wave_kernel's kSpec).  The flags of a
+// library are host-visible constants of a call and the same for every pass over it; the two specialised values stand
+// for BESST's defaults - extend_paths, scoring, duplicate detection - with a whole-number read_len (its VALUE stays a
+// run-time scalar), one per orientation.  Any other library takes the generic code.
+enum : int { kSpecGeneric = 0, kSpecFr = 1, kSpecRf = 2 };
+
 // obs1 + obs2 < ins_size_threshold for two observations above 25 (so their sum is a whole number in (50, 2^32)) as an
 // unsigned compare against ceil(threshold); the threshold is below 2^30 (api.hip), one that is not positive accepts nothing
 __device__ __forceinline__ uint32_t ins_thr_u32(const ClassifyArgs& a) {
@@ -142,6 +148,62 @@ __device__ __forceinline__ Eval eval_record(const ClassifyArgs& a, bool in_range
     e.n_min = n1 < n2 ? n1 : n2;
     e.n_max = n1 < n2 ? n2 : n1;
     if (n1 < n2) e.bits |= EV_FIRSTMIN;
+    return e;
+}
+
+// eval_record for the specialised lean loop (kSpec != 0: whole-number read_len, extend_paths, scoring), without a branch:
+// every lane computes both observations and both node codes from the rows it gathered - row 0 where it has none - and
+// the record's rules only decide the flags.  Where no flag is set the other fields hold whatever the arithmetic gave;
+// the round reads them behind `reach` / `fishy` only.  The same rules as above, restated:
+//   * the side of an end is (contig direction == read direction) for PosDir and for CheckDir alike;
+//   * an unmapped record fails the link test by its flag, so the quirk's early return needs no statement;
+//   * the four PosDir sums wrap in 32 bits exactly as the low half of their int64 forms.
+// As nested ifs the rules were twenty exec-mask regions per round, each zeroing the result at its merge, and the flags went
+// through a packed word to be tested again; in a coordinate-sorted mate-pair stream the lanes of a round take every path.
+struct EvalFlat {
+    bool cov, fishy, nonuniq, reach, mapq0, case_a, dbl, first_min;
+    int32_t o1, o2;
+    uint32_t n_min, n_max;
+};
+
+__device__ __forceinline__ uint32_t posdir_whole(bool cdir, bool rdir, uint32_t cpos, uint32_t rpos, uint32_t slen,
+                                                 uint32_t clen, uint32_t rl) {
+    const uint32_t fwd = cdir ? cpos + rpos + rl : (slen - cpos) - ((clen - rpos) - rl);
+    const uint32_t rev = cdir ? slen - cpos - rpos : cpos + (clen - rpos);
+    return rdir ? rev : fwd;
+}
+
+template <int kSpec>
+__device__ __forceinline__ EvalFlat eval_record_flat(const ClassifyArgs& a, bool in_range, const ContigRow& c1,
+                                                     const ContigRow& c2, int32_t tid, int32_t mtid, int32_t pos,
+                                                     int32_t mpos, uint32_t flag, uint32_t mapq) {
+    static_assert(kSpec == kSpecFr || kSpec == kSpecRf, "the flat evaluation is the specialised forms'");
+    constexpr bool rf = kSpec == kSpecRf;
+    EvalFlat e;
+    const uint32_t cls1 = c1.w0 >> 29, cls2 = c2.w0 >> 29;
+    const bool present = in_range && cls1 != BESST_CLS_ABSENT && cls2 != BESST_CLS_ABSENT;
+    const uint32_t scaf1 = c1.w0 & kScafIdMask, scaf2 = c2.w0 & kScafIdMask;
+    const bool dir1 = (c1.w0 >> 28) & 1u, dir2 = (c2.w0 >> 28) & 1u;
+    const bool rdir = ((flag & kFlagReverse) != 0u) == rf, mdir = ((flag & kFlagMateReverse) != 0u) == rf;   // (rf: inverted)
+    const bool mq_ok = (int32_t)mapq >= a.min_mapq, mq0 = mapq == 0;
+    const bool other = tid != mtid, apart = scaf1 != scaf2;
+    e.cov = present && (mq_ok || mq0);
+    e.mapq0 = mq0;
+    e.nonuniq = present && other && mq0;
+    e.fishy = present && (flag & kFlagUnmapped) && (flag & kFlagRead1) && apart;
+    const bool link = present && other && (flag & kFlagRead2) && !(flag & kFlagUnmapped) && mq_ok;
+    const bool sm1 = cls1 == BESST_CLS_SMALL, sm2 = cls2 == BESST_CLS_SMALL;
+    const bool case_a = cls1 == BESST_CLS_LARGE && cls2 == BESST_CLS_LARGE && apart;
+    const bool case_b = (sm1 && sm2 && apart) || (sm1 != sm2);
+    e.reach = link && (case_a || case_b);
+    e.case_a = e.dbl = case_a;                               // (extend_paths and scoring: the second call, for G_prime)
+    const uint32_t rl = (uint32_t)a.read_len_int;
+    e.o1 = (int32_t)posdir_whole(dir1, rdir, (uint32_t)c1.ctg_pos, (uint32_t)pos, (uint32_t)c1.scaf_len, (uint32_t)c1.ctg_len, rl);
+    e.o2 = (int32_t)posdir_whole(dir2, mdir, (uint32_t)c2.ctg_pos, (uint32_t)mpos, (uint32_t)c2.scaf_len, (uint32_t)c2.ctg_len, rl);
+    const uint32_t n1 = scaf1 * 2 + (dir1 == rdir ? 1u : 0u), n2 = scaf2 * 2 + (dir2 == mdir ? 1u : 0u);
+    e.n_min = n1 < n2 ? n1 : n2;
+    e.n_max = n1 < n2 ? n2 : n1;
+    e.first_min = n1 < n2;
     return e;
 }
 
@@ -634,11 +696,15 @@ __device__ __forceinline__ int wave_sum_dpp(int v) {     // the sum in every lan
 // loop, and the ring, process(), round_fetch and the last block's element-wise loads - which served one workgroup of C3's
 // 24 415 - are not compiled, nor is the ring's 7 KB of LDS allocated.  The stream's partial last block is a launch of the
 // general form over one block; block0 is the number of the launch's first block.
-template <bool kRuns, int kBits, bool kLean = false>
+// kSpec (lean form only): the library's flags compiled in - kSpecFr / kSpecRf, chosen by launch_classify_scan from
+// ClassifyArgs when read_len is whole and extend_paths, no_score and detect_dup have BESST's defaults.  The two fp64
+// bodies of posdir, the uniform branches on the flags and the scalars that held them leave the evaluation round.
+template <bool kRuns, int kBits, bool kLean = false, int kSpec = kSpecGeneric>
 __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
     ClassifyArgs a, unsigned long long* __restrict__ aligned, uint64_t* __restrict__ seg_keys,
     uint64_t* __restrict__ seg_payload, SummView summ, uint32_t* __restrict__ run_status, uint32_t block0) {
     static_assert(!kLean || kBits == 3, "the lean form reads the side stream");
+    static_assert(kLean || kSpec == kSpecGeneric, "only the lean form is specialised");
     __shared__ uint32_t s_buf[kLean ? 1 : 5][kLean ? 1 : kFwRing];   // tid, mtid, pos, mpos, flag | mapq << 16 of the queued candidates
     __shared__ unsigned short s_qlen[kLean ? 1 : kFwRing];
     __shared__ uint32_t s_ph[kRuns ? 1 : 256];            // the sort's two digit histograms, 16 bits per counter (<= 16 384 tuples)
@@ -771,18 +837,27 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
             asm volatile("" : "+v"(c1.w0), "+v"(c1.scaf_len), "+v"(c1.ctg_pos), "+v"(c1.ctg_len));
             asm volatile("" : "+v"(c2.w0), "+v"(c2.scaf_len), "+v"(c2.ctg_pos), "+v"(c2.ctg_len));
         }
-        const Eval e = eval_record(a, in_range, c1, c2, tid, mtid, pos, mpos, fm & 0xffffu, fm >> 16);
+        EvalFlat e;
+        if constexpr (kSpec != kSpecGeneric) {
+            e = eval_record_flat<kSpec>(a, in_range, c1, c2, tid, mtid, pos, mpos, fm & 0xffffu, fm >> 16);
+        } else {
+            const Eval g = eval_record(a, in_range, c1, c2, tid, mtid, pos, mpos, fm & 0xffffu, fm >> 16);
+            e.cov = (g.bits & EV_COV) != 0; e.fishy = (g.bits & EV_FISHY) != 0; e.nonuniq = (g.bits & EV_NONUNIQ) != 0;
+            e.reach = (g.bits & EV_REACH) != 0; e.mapq0 = (g.bits & EV_MAPQ0) != 0; e.case_a = (g.bits & EV_CASEA) != 0;
+            e.dbl = (g.bits & EV_DOUBLE) != 0; e.first_min = (g.bits & EV_FIRSTMIN) != 0;
+            e.o1 = g.o1; e.o2 = g.o2; e.n_min = g.n_min; e.n_max = g.n_max;
+        }
         // (the coverage credited with the streamed records is taken back when a contig is not in the table)
         // (kBits == 3, a block read from the side stream: an entry was credited on its mapq alone - also when its `mtid`
         // is no reference of the header, which the streaming half cannot see)
-        const bool back = in_range ? !(e.bits & EV_COV)
+        const bool back = in_range ? !e.cov
                                    : (side_rounds && live && (uint32_t)tid < (uint32_t)a.n_contigs);
         if (back && ((int32_t)(fm >> 16) >= a.min_mapq || (fm >> 16) == 0u))
             cov_add(tid, 0ull - (unsigned long long)qlen);
-        const bool reach = live && (e.bits & EV_REACH), fishy = live && (e.bits & EV_FISHY);
-        const bool mapq0 = (e.bits & EV_MAPQ0) != 0, case_a = (e.bits & EV_CASEA) != 0;
-        const bool dbl = (e.bits & EV_DOUBLE) != 0;
-        c_nonuniq_fishy += ((live && (e.bits & EV_NONUNIQ)) ? 1u : 0u) | (fishy ? 0x10000u : 0u);
+        const bool reach = live && e.reach, fishy = live && e.fishy;
+        const bool mapq0 = e.mapq0, case_a = e.case_a;
+        const bool dbl = e.dbl;
+        c_nonuniq_fishy += ((live && e.nonuniq) ? 1u : 0u) | (fishy ? 0x10000u : 0u);
         const int32_t o1 = e.o1, o2 = e.o2;
         const unsigned long long has_mask = __ballot(reach);
         c_reach_u += __popcll(has_mask);
@@ -810,7 +885,7 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
                 is_head = true;                              // first reaching record of the block: stitch_kernel's
                 emit = accept;
             } else {
-                const CEDelta d = create_edge(o1, o2, p1, p2, accept, dbl, mapq0, a.detect_dup != 0);
+                const CEDelta d = create_edge(o1, o2, p1, p2, accept, dbl, mapq0, kSpec ? true : a.detect_dup != 0);
                 c_count_nus += (uint32_t)d.count | ((uint32_t)d.nus << 16);
                 c_dup_long += (uint32_t)d.dup | ((uint32_t)d.too_long << 16);
                 emit = d.keep;
@@ -818,9 +893,10 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         }
         const unsigned long long emit_mask = __ballot(emit);
         const int slot = st_emit + below_cnt(emit_mask);
-        const uint32_t mask_a = a.no_score ? BESST_MASK_GPRIME : (BESST_MASK_G | (a.extend_paths ? BESST_MASK_GPRIME : 0u));
+        const uint32_t mask_a = kSpec ? (BESST_MASK_G | BESST_MASK_GPRIME)
+                              : a.no_score ? BESST_MASK_GPRIME : (BESST_MASK_G | (a.extend_paths ? BESST_MASK_GPRIME : 0u));
         const uint32_t mask = case_a ? mask_a : BESST_MASK_GPRIME;
-        const bool first_min = (e.bits & EV_FIRSTMIN) != 0;
+        const bool first_min = e.first_min;
         const uint32_t lo = fishy ? 0u : (uint32_t)(first_min ? o1 : o2);
         const uint32_t hi = fishy ? 0u : ((uint32_t)(first_min ? o2 : o1) | (mask << 30));
         const uint64_t key = ((((uint64_t)e.n_min << a.node_bits) | e.n_max) << 1) | (fishy ? 1u : 0u);
@@ -1959,10 +2035,25 @@ int launch_classify_scan(hipStream_t s, const ClassifyArgs& a, int64_t* aligned,
             // the lean form over the full blocks, the general form over the stream's partial last block (both under the
             // one scope and the one kernel name)
             const uint32_t full = (uint32_t)(a.n / kClsTile);
-            if (full && group_runs)
-                hipLaunchKernelGGL((fused_wave_kernel<true, 3, true>), dim3(full), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, 0u);
-            else if (full)
-                hipLaunchKernelGGL((fused_wave_kernel<false, 3, true>), dim3(full), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, 0u);
+            // the library's flags compiled in (kSpec) where they are BESST's defaults and read_len is a whole number;
+            // BESST_LOOP_SPEC=0 (A/B runs, tests): the generic lean form for every library - read at every call, like
+            // BESST_STITCH_SPAN, so that a test can hold both forms against each other in one process
+            const char* const spec_env = getenv("BESST_LOOP_SPEC");
+            const bool spec = !(spec_env && atoi(spec_env) == 0) && a.read_len_int >= 0 && a.extend_paths != 0 && a.no_score == 0 && a.detect_dup != 0;
+            const int form = spec ? (a.rf != 0 ? kSpecRf : kSpecFr) : kSpecGeneric;
+#define BESST_LAUNCH_LEAN(RUNS, SPEC)                                                                                   \
+    hipLaunchKernelGGL((fused_wave_kernel<RUNS, 3, true, SPEC>), dim3(full), dim3(64), 0, s, a, al, w.seg_keys,        \
+                       w.seg_payload, w.summ, w.run_status, 0u)
+            if (full && group_runs) {
+                if (form == kSpecFr) BESST_LAUNCH_LEAN(true, kSpecFr);
+                else if (form == kSpecRf) BESST_LAUNCH_LEAN(true, kSpecRf);
+                else BESST_LAUNCH_LEAN(true, kSpecGeneric);
+            } else if (full) {
+                if (form == kSpecFr) BESST_LAUNCH_LEAN(false, kSpecFr);
+                else if (form == kSpecRf) BESST_LAUNCH_LEAN(false, kSpecRf);
+                else BESST_LAUNCH_LEAN(false, kSpecGeneric);
+            }
+#undef BESST_LAUNCH_LEAN
             if (full < nblocks && group_runs)
                 hipLaunchKernelGGL((fused_wave_kernel<true, 3>), dim3(nblocks - full), dim3(64), 0, s, a, al, w.seg_keys, w.seg_payload, w.summ, w.run_status, full);
             else if (full < nblocks)

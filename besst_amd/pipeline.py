@@ -310,6 +310,9 @@ class DeviceGraphBuilder(object):
 
     def reduce(self, keys=None, payload=None, n_tuples_ptr=None, capacity=None, first_map=None):
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        # (the repeat closures below are kept in self._redo: they find the builder through a weak reference, so that a
+        # builder that is dropped frees its device buffers at once and not at some later garbage collection)
+        me = weakref.ref(self)
         if keys is None and payload is None and n_tuples_ptr is None and capacity is None and first_map is None:
             args = self._args.get('reduce')
             if args is None:
@@ -323,6 +326,7 @@ class DeviceGraphBuilder(object):
                 spec = self._args['presort'][0]
 
                 def again():
+                    self = me()
                     # (valid for reset -> classify -> reduce passes, which is what step() runs: the repeat below resets the
                     # state and classifies the LAST record set only - a caller that classified several record sets into one
                     # state without reset() must repeat them itself, with sort_flags |= REDUCE_NO_RUNS set beforehand)
@@ -340,6 +344,7 @@ class DeviceGraphBuilder(object):
                     _lib.check(self.lib.besst_dev_reduce_presorted(C.c_void_p(st), *args, C.byref(spec)), 'dev_reduce')
             else:
                 def again():
+                    self = me()
                     st = torch.cuda.current_stream(self.device).cuda_stream
                     _lib.check(self.lib.besst_dev_reduce_flags(C.c_void_p(st), *args, self.sort_flags), 'dev_reduce')
             self._redo = again
@@ -358,6 +363,7 @@ class DeviceGraphBuilder(object):
                 _p(self.ws2), self.ws2.numel(), _p(first_map), self.key_base)
 
         def again():
+            self = me()
             st = torch.cuda.current_stream(self.device).cuda_stream
             _lib.check(self.lib.besst_dev_reduce_flags(C.c_void_p(st), *args, self.sort_flags), 'dev_reduce')
         self._redo = again
