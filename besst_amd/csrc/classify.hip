@@ -1093,8 +1093,9 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         // in odd iterations and consumed in even ones, B the other way round; `pend` and `ent` are rewritten only after
         // their last use.  No register a load of the same iteration writes is copied at the back edge - only the two
         // nibble sets, loaded an iteration and a half before.  The nibble bytes stay as they were loaded until a
-        // sub-tile is processed (a shift at the load would wait for them on the spot).  An odd number of iterations
-        // is rounded up: the extra one is past both the sub-tiles and the rounds and goes through the same code.
+        // sub-tile is processed (a shift at the load would wait for them on the spot).  The loop runs while rounds
+        // remain (phase 1); the sub-tiles behind the last round are streamed by a loop without steps 2 and 3 (phase 2,
+        // below).
         const int32_t* const b_tid = a.tid + block_base;
         const int32_t* const b_mtid = a.mtid + block_base;
         const uint8_t* const b_mapq = a.mapq + block_base;
@@ -1109,7 +1110,9 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         struct ColsB { uint32_t mate, run, set; };                         // the bytes that hold the lane's three nibbles
         struct ColsQ { uint32_t mapq; uint2 qlen; };
         struct ColsT { int4 tid, mtid; };
-        struct Ent { int32_t tid, mtid, pos, mpos; uint32_t fq, mapq; };
+        // (mapq stays the byte it was loaded as until rows() packs it: widened at the load, with phase 1 a loop that may
+        // not run at all, the widening stood at the back edge behind a vmcnt(0) on the entry loads just issued)
+        struct Ent { int32_t tid, mtid, pos, mpos; uint32_t fq; uint8_t mapq; };
         typedef unsigned int v2u __attribute__((ext_vector_type(2)));
         // (the lane's four records begin at block_base + 4 li: their bits are a nibble of byte li / 2 of the block's, the
         // high one in odd lanes - a sub-tile begins at an even li)
@@ -1158,14 +1161,16 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
             const bool live = lane < q.cnt;
             q.tid = live ? v.tid : -1; q.mtid = live ? v.mtid : -1;
             q.pos = live ? v.pos : 0; q.mpos = live ? v.mpos : 0;
-            q.fm = live ? ((v.fq & 0xffffu) | (v.mapq << 16)) : 0u;
+            q.fm = live ? ((v.fq & 0xffffu) | ((uint32_t)v.mapq << 16)) : 0u;
             q.qlen = live ? (v.fq >> 16) : 0u;
             const bool in_range = live && (uint32_t)q.tid < (uint32_t)a.n_contigs && (uint32_t)q.mtid < (uint32_t)a.n_contigs;
             q.c1 = a.table[in_range ? q.tid : 0];
             q.c2 = a.table[in_range ? q.mtid : 0];
             return q;
         };
-        // a sub-tile on one contig: the wave's running sum
+        // a sub-tile on one contig: the wave's running sum.  (Summed per lane and reduced only when the contig changes or
+        // the block ends - six DPP adds and a lane read less per sub-tile - it measured no faster, neither alone nor on top
+        // of the two phases: profiles/README.md.)
         auto credit = [&](int32_t ref, int mine) __attribute__((always_inline)) {
             const int s = wave_sum_dpp(mine);
             if (ref != run_tid) {
@@ -1232,11 +1237,23 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
         ColsB bA = load_b(0), bB = load_b(1), bC = bA, bD = bB;
         ColsQ qA = load_q(0), qB = qA;
         ColsT tA = load_t(0, bA), tB = tA;
-        Ent ent = load_e(0);
         Round pend;                                          // the round whose rows are in flight (cnt == 0: none)
         pend.cnt = 0; pend.tid = pend.mtid = -1; pend.pos = pend.mpos = 0; pend.fm = pend.qlen = 0;
         pend.c1 = a.table[0]; pend.c2 = pend.c1;
-        const int iters = ((n_rounds > kSubs ? n_rounds : kSubs) + 1) & ~1;
+        // Two phases.  Phase 1 pairs a round with a sub-tile while rounds remain (an odd number is rounded up: the extra
+        // iteration's round is empty and goes through the same code; more rounds than sub-tiles: the rest without
+        // sub-tiles).  Phase 2 streams the sub-tiles that are left and touches neither entries nor rows: on a library
+        // with an eighth of its records in the set that is half of the iterations, in which every lane used to load
+        // entry 0 and row 0, compute their addresses and run the round's selects for a round that did not exist - and
+        // whose loads stood in the in-order queue in front of the columns the streaming half waits for.  Phase 1 ends on
+        // a whole pair, so phase 2 finds the column buffers in the roles of an even iteration.
+        const int iters = (n_rounds + 1) & ~1;              // phase 1's iterations
+        Ent ent;
+        ent.tid = ent.mtid = -1; ent.pos = ent.mpos = 0; ent.fq = 0u; ent.mapq = 0;
+        if (n_rounds) ent = load_e(0);                       // uniform: a block without entries reads none
+        // (where phase 2 begins is carried out of the loop, not read from `iters` again: with the bound as phase 2's start
+        // the compiler spilled 59 scalars, not 41)
+        int p2 = 0;
         for (int it = 0; it < iters; it += 2) {
             // ---- even iteration: columns into B, sub-tile from A
             tB = load_t(it + 1, bB);
@@ -1255,8 +1272,37 @@ __global__ __launch_bounds__(64, BESST_FW_MIN_WAVES) void fused_wave_kernel(
             ent = load_e(it + 2);
             if (it + 1 < kSubs) stream(qB, bB, tB);          // uniform
             bA = bC; bB = bD;
+            p2 = it + 2;
         }
-        if (pend.cnt) round_finish(pend);
+        if (p2 < kSubs) {                                    // uniform
+            int it = p2;
+            // ---- phase 2, its first pair: the last round of phase 1 is finished behind this pair's column loads - its
+            // rows had the streaming half of phase 1's last iteration to arrive, the wait is a counted one
+            tB = load_t(it + 1, bB);
+            qB = load_q(it + 1);
+            bC = load_b(it + 2);
+            bD = load_b(it + 3);
+            if (pend.cnt) round_finish(pend);                // uniform
+            stream(qA, bA, tA);
+            tA = load_t(it + 2, bC);
+            qA = load_q(it + 2);
+            stream(qB, bB, tB);
+            bA = bC; bB = bD;
+            // ---- phase 2: the same prefetch distance, the same roles of A and B, the streaming half only
+            for (it += 2; it < kSubs; it += 2) {
+                tB = load_t(it + 1, bB);
+                qB = load_q(it + 1);
+                bC = load_b(it + 2);
+                bD = load_b(it + 3);
+                stream(qA, bA, tA);
+                tA = load_t(it + 2, bC);
+                qA = load_q(it + 2);
+                stream(qB, bB, tB);
+                bA = bC; bB = bD;
+            }
+        } else if (pend.cnt) {
+            round_finish(pend);                              // no phase 2: behind phase 1
+        }
     } else if (kBits != 3 && block_base + kClsTile <= a.n) {
         // A block that lies inside the stream (all but the last): ONE wait per sub-tile.  By the counters a wave of the
         // unpipelined loop sat in s_waitcnt for 72 % of its life - tid / mtid first, then pos / mpos / flag where they
