@@ -21,7 +21,8 @@ copy and the file write of chunk c running while the kernels of chunk c + 1 do.
 FASTA itself (csrc/fasta.hip: the file's bytes are parsed in HBM by the rules of runBESST:45-74); ``C_dict`` then holds
 :class:`SequenceRef` handles instead of strings.  A file that begins with the gzip magic is inflated first: a BGZF file
 (what ``--bgzf_outputs`` and ``bgzip`` write) on the device, block by block at its place in the text
-(:func:`_upload_bgzf_file`); any other gzip file by zlib on the host (:func:`_upload_gzip_host`).  Like the rest of the package there is no CPU path: without
+(:func:`_upload_bgzf_file`); any other gzip file by zlib on the host (:func:`_upload_gzip_host`) -
+or, with ``gzip_on_gpu``, a one-member file on the device as well (:func:`_upload_gzip_device`, csrc/gzip_stream.hip).  Like the rest of the package there is no CPU path: without
 the library or a GPU these calls raise :class:`besst_amd._lib.BesstDeviceError`.
 """
 from __future__ import print_function
@@ -227,9 +228,10 @@ class SequenceStore(object):
         return cls([c.name for c in objs], [c.sequence for c in objs], device=device)
 
     inflate = None
+    inflate_stats = None
 
     @classmethod
-    def from_fasta(cls, path, device=0, tile_bytes=None, blocks_per_launch=None):
+    def from_fasta(cls, path, device=0, tile_bytes=None, blocks_per_launch=None, gzip_on_gpu=False, gzip_chunk_bytes=None):
         """The store of a contig FASTA, parsed on the device (csrc/fasta.hip) with the rules of the reference's
         ReadInContigseqs (runBESST:45-74): one row per header line in file order (``names``); ``index[name]`` is the row
         of the name's last occurrence.  ValueError: a byte outside ASCII, a header without a name, a contig of 2^31 bases
@@ -241,25 +243,43 @@ class SequenceStore(object):
         of the store says which: None, 'device' or 'host'.  FastaError with the COMPRESSED offset of the block or member
         at fault: a CRC-32 or ISIZE that is not the inflated bytes', a file that ends inside a member, bytes behind the
         last member that are none, data zlib does not inflate.  The parser's own errors then count bytes of the
-        inflated text."""
+        inflated text.
+
+        ``gzip_on_gpu``: a gzip file that is not BGZF - ``gzip``'s own output, one member - is inflated on the device too
+        (:func:`_upload_gzip_device`: block starts found by probing, chunks of ``gzip_chunk_bytes`` compressed bytes
+        decoded against windows that are resolved afterwards); ``inflate`` is then 'device_gzip'.  Whatever the device
+        does not take or finds damaged - several members, an odd header, DEFLATE data, ISIZE or a CRC-32 that is wrong,
+        memory that runs out - is read on the host exactly as without the flag, errors included; ``inflate`` is 'host'
+        then and ``inflate_stats['status']`` names the device's reason.  ``inflate_stats``: chunks, candidates (chunks in
+        which a block start was found), live (chunks that were decoded side by side), text_bytes, status (None: the
+        device's gzip path was not tried).  ``gzip_chunk_bytes``: a multiple of 16 in 256..2^24 (GZIP_CHUNK_BYTES)."""
+        chunk = int(GZIP_CHUNK_BYTES if gzip_chunk_bytes is None else gzip_chunk_bytes)
+        if chunk < 256 or chunk > (1 << 24) or chunk % 16:
+            raise ValueError('gzip_chunk_bytes must be a multiple of 16 in 256..2^24')
         torch, dev = _torch_device(device)
+        stats = dict(chunks=0, candidates=0, live=0, text_bytes=0, status=None)
         with open(path, 'rb') as fh:
             gz = fh.read(2) == GZIP_MAGIC
         with torch.cuda.device(dev):
             if gz:
-                text, n, inflate = _upload_gzip_file(torch, dev, path, blocks_per_launch)
+                try:
+                    text, n, inflate = _upload_gzip_file(torch, dev, path, blocks_per_launch, chunk if gzip_on_gpu else None, stats)
+                except FastaError as exc:
+                    exc.inflate_stats = stats                    # (what the device made of the file before the host read it)
+                    raise
             else:
                 (text, n), inflate = _upload_file(torch, dev, path), None
             try:
                 parsed = parse_fasta_text(text, n, tile_bytes)
             except FastaError as exc:
-                if inflate is None:
-                    raise
-                raise FastaError('%s (bytes of the inflated text: the file is compressed)' % exc, exc.offset)
+                if inflate is not None:
+                    exc = FastaError('%s (bytes of the inflated text: the file is compressed)' % exc, exc.offset)
+                exc.inflate_stats = stats
+                raise exc
             del text
         self = cls.__new__(cls)
         self.device = dev
-        self.inflate = inflate
+        self.inflate, self.inflate_stats = inflate, stats
         self._pool, self.pool_ptr, self.pool_bytes = parsed['pool'], parsed['pool'].data_ptr() + EMIT_PAD, parsed['pool_bytes']
         self._off, self._len = parsed['ctg_off'], parsed['ctg_len']
         self.offsets, self.lengths = self._off.cpu().numpy(), self._len.cpu().numpy()
@@ -377,7 +397,9 @@ def filter_contigs(contigs, filter_length, Information=None):
 
 
 class FastaError(ValueError):
-    """The contig FASTA cannot be read; ``offset``: the byte of the file at fault."""
+    """The contig FASTA cannot be read; ``offset``: the byte of the file at fault.  ``inflate_stats``: from_fasta's, where a
+    compressed file was at fault."""
+    inflate_stats = None
 
     def __init__(self, message, offset):
         ValueError.__init__(self, message)
@@ -450,13 +472,18 @@ def _first_bad(word):
     return None if bad == NO_ERROR else (bad >> 8, bad & 0xff)
 
 
-def _upload_gzip_file(torch, dev, path, blocks_per_launch=None):
-    """A file that begins with the gzip magic -> (text, n, 'device' or 'host'), text as _upload_file leaves it."""
+def _upload_gzip_file(torch, dev, path, blocks_per_launch=None, gzip_chunk_bytes=None, stats=None):
+    """A file that begins with the gzip magic -> (text, n, 'device', 'device_gzip' or 'host'), text as _upload_file leaves
+    it.  ``gzip_chunk_bytes``: a file that is not BGZF is tried on the device first (``stats``: what that left)."""
     n_blocks, total, end, size = bgzf_walk(path)
     if end == size:
         got = _upload_bgzf_file(torch, dev, path, n_blocks, total, blocks_per_launch)
         if got is not None:
             return got[0], got[1], 'device'
+    elif gzip_chunk_bytes:
+        got = _upload_gzip_device(torch, dev, path, gzip_chunk_bytes, {} if stats is None else stats)
+        if got is not None:
+            return got[0], got[1], 'device_gzip'
     text, n = _upload_gzip_host(torch, dev, path)
     return text, n, 'host'
 
@@ -553,6 +580,100 @@ def _upload_bgzf_file(torch, dev, path, n_blocks, total, blocks_per_launch=None)
     raise FastaError('the BGZF block at byte %d of the compressed FASTA file (block %d) is damaged: %s' % (
         offset, block, 'its CRC-32 is not that of its inflated bytes' if reason == BGZF_BAD_CRC
         else 'it does not inflate to ISIZE bytes'), offset)
+
+
+GZIP_CHUNK_BYTES = 65536                 # compressed bytes per chunk of the device's gzip inflate
+GZIP_INFO_WORDS = 8                      # include/besst_amd.h: BESST_GZIP_INFO_*
+GZIP_HEADER_ROOM = 1 << 17               # bytes of the file in which the member's header must end
+GZIP_STATUS = ('ok', 'block_type', 'stored_length', 'code_lengths', 'oversubscribed_code', 'bad_code', 'bad_distance',
+               'output_overrun', 'input_overrun', 'isize', 'crc', 'trailing_bytes')
+GZIP_STEPS = (('probe', 'count', 'link'), ('decode', 'windows', 'translate', 'crc'))
+GZIP_KERNEL_TIMES = None                 # a dict here (tools/time_fasta_ingest.py) is filled with the steps' milliseconds
+
+
+def gzip_header_bytes(head):
+    """The length of the gzip member header that ``head`` (the file's first bytes) begins with, i.e. where the DEFLATE
+    data starts; None: not a header this package's device path takes (magic, CM = 8, reserved flag bits, a field that
+    does not end inside ``head``).  RFC 1952: FEXTRA, FNAME, FCOMMENT and FHCRC are skipped."""
+    if len(head) < 10 or head[:2] != GZIP_MAGIC or head[2] != 8 or head[3] & 0xe0:
+        return None
+    flg, at = head[3], 10
+    if flg & 4:                                                  # FEXTRA
+        if at + 2 > len(head):
+            return None
+        at += 2 + (head[at] | head[at + 1] << 8)
+    for bit in (8, 16):                                          # FNAME, FCOMMENT: zero-terminated
+        if flg & bit:
+            end = head.find(b'\0', at) if at <= len(head) else -1
+            if end < 0:
+                return None
+            at = end + 1
+    if flg & 2:                                                  # FHCRC
+        at += 2
+    return at if at <= len(head) else None
+
+
+def _gzip_steps(torch, names, call):
+    """call(steps) for all steps at once, or - GZIP_KERNEL_TIMES - one by one between two events each"""
+    times = GZIP_KERNEL_TIMES
+    if times is None:
+        call(0)
+        return
+    for k, name in enumerate(names):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        call(1 << k)
+        t1.record()
+        t1.synchronize()
+        times[name] = t0.elapsed_time(t1)
+
+
+def _upload_gzip_device(torch, dev, path, chunk_bytes, stats):
+    """A file that is ONE gzip member, inflated on the device (csrc/gzip_stream.hip): the compressed file goes up as it is
+    (_upload_file); besst_dev_gzip_plan finds the chunks that can be decoded side by side and the text's size - the one
+    read from the device in the middle -, besst_dev_gzip_inflate decodes, resolves the windows and checks the CRC-32.
+    -> (text, n) as _upload_file, or None with stats['status'] saying why: the caller reads the file on the host, which
+    also words the error where the file is damaged.  Every temporary is let go before that."""
+    lib = _lib.load()
+    p = _C.c_void_p
+    size = os.path.getsize(path)
+    with open(path, 'rb') as fh:
+        data_off = gzip_header_bytes(fh.read(GZIP_HEADER_ROOM))
+    if data_off is None or size < data_off + 8:
+        stats['status'] = 'header'
+        return None
+    plan_bytes = lib.besst_dev_gzip_plan_workspace_bytes(size, data_off, chunk_bytes)
+    if not plan_bytes:
+        stats['status'] = 'file_size'
+        return None
+    stream = p(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        comp, _ = _upload_file(torch, dev, path)
+        plan = torch.empty(plan_bytes, dtype=torch.uint8, device=dev)
+        info = torch.zeros(GZIP_INFO_WORDS, dtype=torch.int64, device=dev)
+        _gzip_steps(torch, GZIP_STEPS[0], lambda steps: _lib.check(lib.besst_dev_gzip_plan(
+            stream, p(comp.data_ptr()), size, data_off, chunk_bytes, steps, p(plan.data_ptr()), plan_bytes, p(info.data_ptr())),
+            'besst_dev_gzip_plan'))
+        status, n, chunks, candidates, live = info.cpu().tolist()[:5]     # the one read in the middle: the text's size
+        stats.update(chunks=chunks, candidates=candidates, live=live, text_bytes=n, status=GZIP_STATUS[status])
+        if status:
+            return None
+        ws_bytes = lib.besst_dev_gzip_inflate_workspace_bytes(n, live)
+        if not ws_bytes:
+            stats['status'] = 'file_size'
+            return None
+        text = torch.empty(n + EMIT_PAD, dtype=torch.uint8, device=dev)
+        text[n:].zero_()
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _gzip_steps(torch, GZIP_STEPS[1], lambda steps: _lib.check(lib.besst_dev_gzip_inflate(
+            stream, p(comp.data_ptr()), size, data_off, chunk_bytes, steps, p(plan.data_ptr()), live, n, p(text.data_ptr()),
+            p(ws.data_ptr()), ws_bytes, p(info.data_ptr())), 'besst_dev_gzip_inflate'))
+        status = int(info[0].item())
+        stats.update(status=GZIP_STATUS[status], plan_bytes=int(plan_bytes), workspace_bytes=int(ws_bytes))
+        return (text, n) if not status else None
+    except torch.cuda.OutOfMemoryError:
+        stats['status'] = 'allocation'
+        return None
 
 
 def _gzip_members(fh, piece=1 << 20):

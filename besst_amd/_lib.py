@@ -257,6 +257,11 @@ _SIGNATURES = {
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     'besst_dev_bgzf_inflate_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
     'besst_dev_bgzf_inflate': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_size_t, _P]),
+    'besst_dev_gzip_plan_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    'besst_dev_gzip_plan': (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, C.c_size_t, _P]),
+    'besst_dev_gzip_inflate_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
+    'besst_dev_gzip_inflate': (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P,
+                                         C.c_size_t, _P]),
 }
 
 _lib = None

@@ -7,7 +7,9 @@ Flag names and defaults follow runBESST:254-402 for everything the hot path read
 ``CreateGraph.PE`` and writes Statistics.txt plus the scored edge tables of G and G' as TSV.  With ``--scaffolds -y`` it
 goes on like runBESST's loop without path extension: the graph is linearised, the paths become scaffolds, and every pass
 writes ``pass<n>/Scaffolds-pass<n>.fa`` with its ``.agp`` and ``.gff`` (the sequence work on the GPU).  With
-``--fasta_on_gpu`` the contig FASTA is parsed on the GPU into the sequence store instead of line by line in Python.  With
+``--fasta_on_gpu`` the contig FASTA is parsed on the GPU into the sequence store instead of line by line in Python; a BGZF file is
+inflated there as well, and with ``--gzip_on_gpu`` so is a plain ``gzip`` file (one member; anything else is read by zlib on
+the host, as without the flag).  With
 ``--outputs_on_gpu`` the AGP and GFF text is formatted on the GPU too, and ``repeats.fa`` / ``low_coverage_contigs.fa`` are
 written from the sequence store in one go where the contigs live there (``--fasta_on_gpu``).  ``--final_fasta`` leaves the
 directory as runBESST does without --separate_repeats: ``pass<n>/Scaffolds_pass<n>.fa`` holds the scaffolds followed by
@@ -93,6 +95,10 @@ def build_parser():
                          'sequence store (GenerateOutput.SequenceStore.from_fasta); the sequences do not pass through '
                          'Python strings.  A BGZF file (bgzip, --bgzf_outputs) is inflated on the GPU too; any other gzip '
                          'file by zlib on the host')
+    ap.add_argument('--gzip_on_gpu', dest='gzip_on_gpu', action='store_true',
+                    help="with --fasta_on_gpu: a contig FASTA that is plain gzip (gzip's own output, one member) is inflated on "
+                         'the GPU as well - block starts found by probing, chunks decoded side by side, CRC-32 checked; what '
+                         'the GPU does not take is read by zlib on the host as without the flag; needs --fasta_on_gpu')
     ap.add_argument('--outputs_on_gpu', dest='outputs_on_gpu', action='store_true',
                     help='format info-pass<n>.agp / .gff on the GPU, and write repeats.fa / low_coverage_contigs.fa '
                          'from the sequence store in one go where the contigs live there (--fasta_on_gpu)')
@@ -225,6 +231,8 @@ def main(argv=None):
         sys.exit('--final_fasta needs --scaffolds: Scaffolds_pass<n>.fa is the scaffold FASTA followed by the repeats')
     if args.bgzf_outputs and not args.scaffolds:
         sys.exit('--bgzf_outputs needs --scaffolds: the file it compresses is the scaffold FASTA')
+    if args.gzip_on_gpu and not args.fasta_on_gpu:
+        sys.exit('--gzip_on_gpu needs --fasta_on_gpu: it is the sequence store that reads the compressed file on the GPU')
     if args.max_contig_overlap < 0 or args.max_contig_overlap > GO.MAX_CONTIG_OVERLAP_LIMIT:
         sys.exit('-max_contig_overlap must lie in 0..%d' % GO.MAX_CONTIG_OVERLAP_LIMIT)
     rank, joined = join_process_group()
@@ -259,7 +267,7 @@ def _run(args, rank):
     fasta_on_gpu, filter_length = args.fasta_on_gpu, args.contig_filter_length
     if fasta_on_gpu:
         # file bytes -> HBM -> the store; C_dict holds handles into it (the filtered contigs stay in the pool, unused)
-        store = GO.SequenceStore.from_fasta(args.contigfile) if lead else None
+        store = GO.SequenceStore.from_fasta(args.contigfile, gzip_on_gpu=args.gzip_on_gpu) if lead else None
         C_dict = store.contig_dict(filter_length, Information) if lead else {}
         if lead and args.outputs_on_gpu:
             store.batch_fasta = True

@@ -42,7 +42,8 @@ extern "C" {
  * besst_dev_text_workspace_bytes / besst_dev_text_measure / besst_dev_text_emit / besst_dev_wrap_fasta,
  * besst_dev_bgzf_deflate_bound / besst_dev_bgzf_deflate_workspace_bytes / besst_dev_bgzf_deflate / besst_bgzf_deflate_device;
  * the inflate of a BGZF file in device memory besst_bgzf_walk / besst_bgzf_scan_chunk /
- * besst_dev_bgzf_inflate_workspace_bytes / besst_dev_bgzf_inflate; the run bits of the record layout besst_dev_record_bits
+ * besst_dev_bgzf_inflate_workspace_bytes / besst_dev_bgzf_inflate; of a plain gzip member besst_dev_gzip_plan_workspace_bytes /
+ * besst_dev_gzip_plan / besst_dev_gzip_inflate_workspace_bytes / besst_dev_gzip_inflate; the run bits of the record layout besst_dev_record_bits
  * with the trailing member besst_lib_params.tid_bits (see there); the candidate side stream besst_cand_stream with
  * besst_dev_candidate_offsets_bytes / besst_dev_candidate_stream_bytes / besst_dev_candidate_offsets /
  * besst_dev_candidate_stream, the trailing member besst_lib_params.cand_stream, and besst_dev_record_loop_form. */
@@ -335,6 +336,52 @@ size_t besst_dev_bgzf_inflate_workspace_bytes(int64_t n_blocks, int64_t inflated
 int besst_dev_bgzf_inflate(void* stream, const void* comp, const besst_bgzf_block* blocks, int64_t n_blocks,
                            int64_t block_base, int64_t inflated_bytes, void* dst, void* workspace, size_t workspace_bytes,
                            uint64_t* first_bad);
+
+/* ---- a plain gzip member inflated from device memory into device memory (csrc/gzip_stream.hip; GenerateOutput.py:
+ * SequenceStore.from_fasta(gzip_on_gpu=True)) ---------------------------------------------------------------------------
+ * The file (comp_bytes, 4-byte aligned, readable up to the dword that holds its last byte) is ONE gzip member whose DEFLATE
+ * data begins at byte data_off (the caller parses the gzip header) and whose last eight bytes are the trailer.  The data is
+ * cut into chunks of chunk_bytes (a multiple of 16 in 256..2^24); DESIGN.md section 11.2 has the scheme.  Two calls with one
+ * read of `info` between them (the text's size is not known before):
+ *   besst_dev_gzip_plan_workspace_bytes     the per-chunk words of a file of that geometry; 0: arguments out of range
+ *                          (comp_bytes < data_off + 8, comp_bytes > 2^35, a chunk size that is none).
+ *   besst_dev_gzip_plan    enqueues on `stream`: the probe (a candidate block start per chunk), the count (a wave per chunk:
+ *                          where it lands, the bytes until there) and the link (the live chunks and their places).  Leaves
+ *                          info[0..8) (device): BESST_GZIP_INFO_STATUS (0, or the reason the member is not taken: 1..8 the
+ *                          DEFLATE data of a live chunk, BESST_GZIP_BAD_SIZE the text is not ISIZE bytes modulo 2^32,
+ *                          BESST_GZIP_TRAILING the final block's trailer is not the file's end - another member follows),
+ *                          _TEXT (bytes the member inflates to), _CHUNKS, _CANDIDATES (chunks behind the first that hold a
+ *                          block start), _LIVE (chunks on the chain from chunk 0), _END_BIT, _BAD_CHUNK.
+ *   besst_dev_gzip_inflate_workspace_bytes  two bytes per byte of text (the symbols), a status per live chunk, the CRC's
+ *                          partial values; 0: arguments out of range (n_live < 1).
+ *   besst_dev_gzip_inflate enqueues on `stream`, for the plan in plan_workspace and the n_live and text_bytes read from its
+ *                          info: the decode into symbols, the windows, the translation into text[0, text_bytes) (16-byte
+ *                          aligned) and the CRC-32 against the trailer.  info[BESST_GZIP_INFO_STATUS] (device) is still 0
+ *                          when the text is good; BESST_GZIP_BAD_CRC, or 1..9 from the decode, when it is not (the text's
+ *                          bytes mean nothing then).  No byte outside the buffers is touched whatever the data holds.
+ * steps: 0 = every step; else a bit mask of the steps to enqueue (plan: 1 probe, 2 count, 4 link; inflate: 1 decode,
+ * 2 windows, 4 translate, 8 CRC) - for timing them one by one, in order, on the same buffers.
+ * BESST_ERR_ARG without touching the device: a null pointer, sizes out of range, a misaligned buffer, a workspace smaller
+ * than asked for. */
+#define BESST_GZIP_BAD_SIZE 9
+#define BESST_GZIP_BAD_CRC 10
+#define BESST_GZIP_TRAILING 11
+#define BESST_GZIP_INFO_WORDS 8
+#define BESST_GZIP_INFO_STATUS 0
+#define BESST_GZIP_INFO_TEXT 1
+#define BESST_GZIP_INFO_CHUNKS 2
+#define BESST_GZIP_INFO_CANDIDATES 3
+#define BESST_GZIP_INFO_LIVE 4
+#define BESST_GZIP_INFO_END_BIT 5
+#define BESST_GZIP_INFO_BAD_CHUNK 6
+#define BESST_GZIP_INFO_CRC 7
+size_t besst_dev_gzip_plan_workspace_bytes(int64_t comp_bytes, int64_t data_off, int64_t chunk_bytes);
+int besst_dev_gzip_plan(void* stream, const void* comp, int64_t comp_bytes, int64_t data_off, int64_t chunk_bytes,
+                        int32_t steps, void* workspace, size_t workspace_bytes, uint64_t* info);
+size_t besst_dev_gzip_inflate_workspace_bytes(int64_t text_bytes, int64_t n_live);
+int besst_dev_gzip_inflate(void* stream, const void* comp, int64_t comp_bytes, int64_t data_off, int64_t chunk_bytes,
+                           int32_t steps, const void* plan_workspace, int64_t n_live, int64_t text_bytes, void* text,
+                           void* workspace, size_t workspace_bytes, uint64_t* info);
 
 /* libmetrics sampling (replaces the three `for read in bam_file` scans, libmetrics.py:63,257,293).
  * top_mask[tid] != 0 marks the 1000 longest references.  orientation/min_mapq/read_len as in

@@ -9,8 +9,10 @@
   * wall time of the host path (cli.read_fasta + SequenceStore(names, sequences)) in the same process on the same file,
     in both orders, the page cache warm for both;
   * the same file compressed: as BGZF by GenerateOutput.bgzf_compress (from_fasta inflates it on the device) and by zlib
-    at level 1 as one plain gzip member (from_fasta inflates it on the host) - wall time of from_fasta on the three files,
-    alternating, --gz_reps rounds, with the bytes each form sends over PCIe; and cli.read_fasta on the BGZF file.
+    at levels 1 and 6 as one plain gzip member each (from_fasta inflates them on the host, and with gzip_on_gpu=True on the
+    device: csrc/gzip_stream.hip) - wall time of from_fasta on every file and path, alternating in the same rounds,
+    --gz_reps rounds, median and range, with the bytes each form sends over PCIe; the device gzip path's kernels one by
+    one (a run of their own) and its workspace; and cli.read_fasta on the BGZF file.
 
     python tools/time_fasta_ingest.py --out profiles/fasta_ingest.json
 """
@@ -48,9 +50,9 @@ def write_fasta(path, asm, width=60):
     return os.path.getsize(path)
 
 
-def device_path(path):
+def device_path(path, **kw):
     t0 = time.time()
-    store = GO.SequenceStore.from_fasta(path)
+    store = GO.SequenceStore.from_fasta(path, **kw)
     return store, time.time() - t0
 
 
@@ -63,18 +65,25 @@ def host_path(path):
 
 
 def write_compressed(path, work):
-    """-> {'bgzf': path, 'gzip': path} of the FASTA at ``path``"""
+    """-> {'bgzf': path, 'gzip': path (level 1), 'gzip6': path} of the FASTA at ``path``"""
     with open(path, 'rb') as fh:
         raw = fh.read()
-    out = dict(bgzf=os.path.join(work, 'contigs.bgzf.fa.gz'), gzip=os.path.join(work, 'contigs.gzip.fa.gz'))
+    out = dict(bgzf=os.path.join(work, 'contigs.bgzf.fa.gz'), gzip=os.path.join(work, 'contigs.gzip.fa.gz'),
+               gzip6=os.path.join(work, 'contigs.gzip6.fa.gz'))
     with open(out['bgzf'], 'wb') as fh:
         fh.write(GO.bgzf_compress(raw))
-    comp = zlib.compressobj(1, zlib.DEFLATED, 31)
-    with open(out['gzip'], 'wb') as fh:
-        for at in range(0, len(raw), 64 << 20):
-            fh.write(comp.compress(raw[at:at + (64 << 20)]))
-        fh.write(comp.flush())
+    for kind, level in (('gzip', 1), ('gzip6', 6)):
+        comp = zlib.compressobj(level, zlib.DEFLATED, 31)
+        with open(out[kind], 'wb') as fh:
+            for at in range(0, len(raw), 64 << 20):
+                fh.write(comp.compress(raw[at:at + (64 << 20)]))
+            fh.write(comp.flush())
     return out
+
+
+# what is timed: (name in the report, file, from_fasta's keywords)
+RUNS = (('plain', 'plain', {}), ('bgzf', 'bgzf', {}), ('gzip', 'gzip', {}), ('gzip_device', 'gzip', {'gzip_on_gpu': True}),
+        ('gzip6', 'gzip6', {}), ('gzip6_device', 'gzip6', {'gzip_on_gpu': True}))
 
 
 def compressed_runs(path, n, asm, reps, work):
@@ -84,17 +93,20 @@ def compressed_runs(path, n, asm, reps, work):
         n_blocks = GO.bgzf_walk(files['bgzf'])[0]
         doc = dict(file_bytes={k: os.path.getsize(v) for k, v in files.items()}, bgzf_blocks=n_blocks,
                    # what crosses PCIe on the way in: the file (and 24 bytes of descriptor per block), or the inflated text
-                   pcie_bytes=dict(plain=n, bgzf=os.path.getsize(files['bgzf']) + GO.BGZF_DESC_BYTES * n_blocks, gzip=n),
-                   from_fasta_s=dict(plain=[], bgzf=[], gzip=[]), inflate={})
+                   pcie_bytes=dict(plain=n, bgzf=os.path.getsize(files['bgzf']) + GO.BGZF_DESC_BYTES * n_blocks, gzip=n, gzip6=n,
+                                   gzip_device=os.path.getsize(files['gzip']), gzip6_device=os.path.getsize(files['gzip6'])),
+                   from_fasta_s={name: [] for name, _, _ in RUNS}, inflate={}, gzip_device={})
         for k in files.values():
             with open(k, 'rb') as fh:                            # page cache warm
                 while fh.read(64 << 20):
                     pass
         for rep in range(reps):
-            for kind in ('plain', 'bgzf', 'gzip'):
-                store, took = device_path(files[kind])
+            for kind, which, kw in RUNS:
+                store, took = device_path(files[which], **kw)
                 doc['from_fasta_s'][kind].append(took)
                 doc['inflate'][kind] = store.inflate
+                if kw:
+                    doc['gzip_device'][kind] = dict(store.inflate_stats)
                 if rep == 0:
                     assert store.names == asm['names'] and np.array_equal(store.lengths, asm['lengths'])
                     got = store._pool[GO.EMIT_PAD:GO.EMIT_PAD + store.pool_bytes].cpu().numpy()
@@ -103,6 +115,18 @@ def compressed_runs(path, n, asm, reps, work):
                 store.close()
                 del store
         doc['from_fasta_s_median'] = {k: float(np.median(v)) for k, v in doc['from_fasta_s'].items()}
+        doc['from_fasta_s_range'] = {k: [float(min(v)), float(max(v))] for k, v in doc['from_fasta_s'].items()}
+        # the device gzip path's steps, each between two events and waited for: a run of its own, not one of the timed ones
+        for kind, which, kw in RUNS:
+            if kw:
+                GO.GZIP_KERNEL_TIMES = {}
+                try:
+                    store, _ = device_path(files[which], **kw)
+                    store.close()
+                    del store
+                    doc['gzip_device'][kind]['kernel_ms'] = dict(GO.GZIP_KERNEL_TIMES)
+                finally:
+                    GO.GZIP_KERNEL_TIMES = None
         t0 = time.time()
         seqs = cli.read_fasta(files['bgzf'])
         doc['read_fasta_bgzf_s'] = time.time() - t0
@@ -111,7 +135,7 @@ def compressed_runs(path, n, asm, reps, work):
         doc['reps'] = reps
         return doc
     finally:
-        for kind in ('bgzf', 'gzip'):
+        for kind in ('bgzf', 'gzip', 'gzip6'):
             if os.path.exists(files[kind]):
                 os.remove(files[kind])
 
@@ -121,7 +145,7 @@ def main():
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'fasta_ingest.json'))
     ap.add_argument('--contigs', type=int, default=100_000)
     ap.add_argument('--reps', type=int, default=10)
-    ap.add_argument('--gz_reps', type=int, default=3, help='rounds of from_fasta over the plain, BGZF and gzip file')
+    ap.add_argument('--gz_reps', type=int, default=3, help='rounds of from_fasta over the plain, the BGZF and the gzip files')
     args = ap.parse_args()
     import torch
     asm = OU.seeded_assembly(args.contigs, 3000, 20000, 17)
