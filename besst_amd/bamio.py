@@ -79,6 +79,11 @@ class ResidentBam(object):
     def __len__(self):
         return self._n
 
+    def layout_state(self):
+        """GraphContext.layout_state(): after a device ingest the bit planes and the candidate side stream of the records are
+        there already (all three watermarks at ``len()``), and the first build launches no maker."""
+        return self.ctx.layout_state()
+
     def close(self):
         self.ctx.close()
 

@@ -333,6 +333,53 @@ int besst_ctx_fetch_records(besst_ctx* c, int64_t first, int64_t n, int32_t* tid
     return BESST_OK;
 }
 
+int besst_ctx_layout_state(besst_ctx* c, int64_t* out) {
+    BESST_REQUIRE(c && out, "layout_state: null pointer");
+    const bool stream = c->cs_upto > 0;
+    out[0] = c->n_records;
+    out[1] = c->bits_upto;
+    out[2] = c->tid_bits_upto;
+    out[3] = c->cs_upto;
+    out[4] = stream ? c->cs.n_entries : 0;
+    out[5] = stream ? c->cs.n_refs : 0;
+    out[6] = c->cs_cap_entries;
+    out[7] = c->maker_launches;
+    return BESST_OK;
+}
+
+int besst_ctx_fetch_layout(besst_ctx* c, uint8_t* mate_bits, uint8_t* tid_bits, uint8_t* set_bits, uint32_t* offsets, int32_t* tid,
+                           int32_t* mtid, int32_t* pos, int32_t* mpos, uint32_t* flag_qlen, uint8_t* mapq) {
+    BESST_REQUIRE(c, "fetch_layout: null context");
+    int rc = use_device(c);
+    if (rc) return rc;
+    auto down = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    BESST_HIP_TRY(down(mate_bits, c->mate_bits.p, (size_t)((c->bits_upto + 7) / 8)));
+    BESST_HIP_TRY(down(tid_bits, c->tid_bits.p, (size_t)((c->tid_bits_upto + 7) / 8)));
+    if (c->cs_upto > 0) {
+        const size_t m = (size_t)c->cs.n_entries, cap = (size_t)c->cs_cap_entries;
+        const uint8_t* e = c->cs_entries.p;
+        BESST_HIP_TRY(down(set_bits, c->cs_set.p, (size_t)((c->cs_upto + 7) / 8)));
+        BESST_HIP_TRY(down(offsets, c->cs_off.p, (size_t)((c->cs_upto + kClsTile - 1) / kClsTile + 1) * sizeof(uint32_t)));
+        BESST_HIP_TRY(down(tid, e, m * 4));
+        BESST_HIP_TRY(down(mtid, e + cap * 4, m * 4));
+        BESST_HIP_TRY(down(pos, e + cap * 8, m * 4));
+        BESST_HIP_TRY(down(mpos, e + cap * 12, m * 4));
+        BESST_HIP_TRY(down(flag_qlen, e + cap * 16, m * 4));
+        BESST_HIP_TRY(down(mapq, e + cap * 20, m));
+    }
+    BESST_HIP_TRY(hipStreamSynchronize(c->stream));
+    // the valid prefix only: the bits behind a watermark in the byte that holds it are later records' (or nobody's)
+    auto mask_tail = [](uint8_t* plane, int64_t upto) {
+        if (plane && (upto & 7)) plane[upto >> 3] &= (uint8_t)((1u << (upto & 7)) - 1u);
+    };
+    mask_tail(mate_bits, c->bits_upto);
+    mask_tail(tid_bits, c->tid_bits_upto);
+    if (c->cs_upto > 0) mask_tail(set_bits, c->cs_upto);
+    return BESST_OK;
+}
+
 size_t besst_dev_classify_workspace_bytes(int64_t n_records) { return classify_workspace_bytes(n_records); }
 namespace {
 __global__ __launch_bounds__(256) void copy_words_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, uint32_t n16,
@@ -845,6 +892,7 @@ int besst_ctx_build_graph(besst_ctx* c) {
                 if ((rc = launch_mate_bits(c->stream, c->tid.p, c->mtid.p, upto, n, n, c->mate_bits.p,
                                            runs ? c->tid_bits.p : nullptr)))
                     return rc;
+                ++c->maker_launches;
                 c->bits_upto = n;
                 if (runs) c->tid_bits_upto = n;
             }
@@ -872,6 +920,7 @@ int besst_ctx_build_graph(besst_ctx* c) {
                     if ((rc = launch_cand_offsets(c->stream, n, c->n_contigs, c->tid.p, c->mtid.p, c->flag.p, c->cs_set.p, c->cs_off.p,
                                                   nullptr, nullptr, first)))
                         return rc;
+                    ++c->maker_launches;
                     uint32_t total = 0;
                     BESST_HIP_TRY(hipMemcpyAsync(&total, c->cs_off.p + nblocks, sizeof(total), hipMemcpyDeviceToHost, c->stream));
                     BESST_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -894,6 +943,7 @@ int besst_ctx_build_graph(besst_ctx* c) {
                                                   reinterpret_cast<int32_t*>(e + cap * 12), reinterpret_cast<uint32_t*>(e + cap * 16),
                                                   reinterpret_cast<uint8_t*>(e + cap * 20), (uint32_t)cap, first)))
                         return rc;
+                    ++c->maker_launches;
                     c->cs_upto = n;
                 }
                 c->cs.n_records = n;

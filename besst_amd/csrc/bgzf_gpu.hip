@@ -48,6 +48,7 @@
 
 #include "bgzf_crc.h"
 #include "common.h"
+#include "ingest_layout_core.h"
 
 namespace besst {
 
@@ -1526,77 +1527,267 @@ __global__ __launch_bounds__(kScanThreads) void bam_scan_kernel(const uint8_t* _
     }
 }
 
-// one workgroup per block, a thread per record
+// the record's first nine dwords - block_size, then the 32 fixed bytes - from any alignment
+__device__ __forceinline__ void bam_fixed_fields(const uint8_t* rec, uint32_t* f) {
+    const uintptr_t a = (uintptr_t)rec;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+    const uint32_t sh = (uint32_t)(a & 3u) * 8u;
+    uint32_t x[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) x[k] = w[k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = sh ? (x[k] >> sh) | (x[k + 1] << (32u - sh)) : x[k];
+}
+
+// pysam 0.8.4's qlen (not yet clamped to 16 bits) and alen from the CIGAR (bam_reader.hip's decode has the reasoning);
+// false: a corrupt record - its name and CIGAR do not fit its length -, whose CIGAR is not looked at
+__device__ __forceinline__ bool bam_record_lens(const uint8_t* rec, const uint32_t* f, long long* q_aln_out, long long* ref_len_out) {
+    const uint32_t block_size = f[0];
+    const uint32_t l_read_name = f[3] & 0xffu, n_cigar = f[4] & 0xffffu, l_seq = f[5];
+    long long q_total = 0, ref_len = 0, lead = 0, trail = 0;
+    const bool fits = 32ull + l_read_name + 4ull * n_cigar <= (unsigned long long)block_size;
+    if (fits) {
+        const uint8_t* cg = rec + 36 + l_read_name;
+        bool in_lead = true;
+        for (uint32_t c = 0; c < n_cigar; ++c) {
+            const uint32_t v = ld32u(cg + 4u * c);
+            const uint32_t op = v & 15u, len = v >> 4;
+            if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) q_total += len;
+            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ref_len += len;
+            if (in_lead) {
+                if (op == 4u) lead += len;
+                else if (op != 5u) in_lead = false;
+            }
+        }
+        for (uint32_t c = n_cigar; c-- > 1u;) {
+            const uint32_t v = ld32u(cg + 4u * c);
+            const uint32_t op = v & 15u, len = v >> 4;
+            if (op == 4u) trail += len;
+            else if (op != 5u) break;
+        }
+    }
+    long long q_aln = (l_seq ? (long long)l_seq : q_total) - lead - trail;
+    if (q_aln < 0) q_aln = 0;
+    *q_aln_out = q_aln;
+    *ref_len_out = ref_len;
+    return fits;
+}
+
+// a wave's ballot into a bit plane: lanes 0 and 32 hold the two words (ingest_layout_core.h has the rules)
+__device__ __forceinline__ void plane_put(uint32_t* __restrict__ plane, int64_t word_first, uint32_t bits, bool whole) {
+    uint32_t* w = plane + (word_first >> 5);
+    if (whole) *w = bits;
+    else if (bits) atomicOr(w, bits);
+}
+
+// One workgroup per block, a thread per record.  kLayout: the record's bits go into the three planes as well - the lanes
+// are laid over the records from the plane word that holds the block's first record, so the halves of a wave's ballot are
+// plane words: stored where all 32 records are this block's, ORed into the zeroed plane where the block shares the word
+// with a neighbour - and the block's set records are counted for bam_entry_scan_kernel.  The run bit of the chunk's
+// first record is left 0: the record before it was decoded on another stream (bam_layout_seams_kernel sets it).
+template <bool kLayout>
 __global__ __launch_bounds__(256) void bam_decode_kernel(const uint8_t* __restrict__ inflated, const BgzfBlock* __restrict__ blocks,
                                                          const uint16_t* __restrict__ offs, const uint32_t* __restrict__ count,
                                                          const uint32_t* __restrict__ rec_base, BamColumns col, int64_t out_base,
-                                                         int64_t rel_base, int64_t head_records, uint32_t* __restrict__ flags) {
+                                                         int64_t rel_base, int64_t head_records, uint32_t* __restrict__ flags,
+                                                         BamLayout lay) {
+    __shared__ uint32_t s_set;
     const uint32_t b = blockIdx.x;
     const uint32_t cnt = count[b];
     const uint8_t* base = inflated + (size_t)blocks[b].dst_off_lo + ((size_t)blocks[b].dst_off_hi << 32);
     const uint16_t* o = offs + (size_t)b * kBamBlockRecs;
     const int64_t first = out_base + (int64_t)rec_base[b];
-    for (uint32_t i = threadIdx.x; i < cnt; i += 256u) {
-        const uint8_t* rec = base + o[i];
-        const uintptr_t a = (uintptr_t)rec;
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-        const uint32_t sh = (uint32_t)(a & 3u) * 8u;
-        uint32_t x[10];
-#pragma unroll
-        for (int k = 0; k < 10; ++k) x[k] = w[k];
-        uint32_t f[9];                                       // the record's first nine dwords: block_size, then 32 fixed bytes
-#pragma unroll
-        for (int k = 0; k < 9; ++k) f[k] = sh ? (x[k] >> sh) | (x[k + 1] << (32u - sh)) : x[k];
-        const uint32_t block_size = f[0];
-        const uint32_t l_read_name = f[3] & 0xffu, mapq = (f[3] >> 8) & 0xffu;
-        const uint32_t n_cigar = f[4] & 0xffffu, flag = f[4] >> 16;
-        const uint32_t l_seq = f[5];
-        const int64_t r = first + (int64_t)i;
-        col.tid[r] = (int32_t)f[1];
-        col.pos[r] = (int32_t)f[2];
-        col.mapq[r] = (uint8_t)mapq;
-        col.flag[r] = (uint16_t)flag;
-        col.mtid[r] = (int32_t)f[6];
-        col.mpos[r] = (int32_t)f[7];
-        col.tlen[r] = (int32_t)f[8];
-        long long q_total = 0, ref_len = 0, lead = 0, trail = 0;
-        if (32ull + l_read_name + 4ull * n_cigar > (unsigned long long)block_size) {
-            atomicOr(&flags[0], 1u);                         // corrupt record
-        } else {
-            // pysam 0.8.4's qlen / alen (bam_reader.hip's decode has the reasoning)
-            const uint8_t* cg = rec + 36 + l_read_name;
-            bool in_lead = true;
-            for (uint32_t c = 0; c < n_cigar; ++c) {
-                const uint32_t v = ld32u(cg + 4u * c);
-                const uint32_t op = v & 15u, len = v >> 4;
-                if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) q_total += len;
-                if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ref_len += len;
-                if (in_lead) {
-                    if (op == 4u) lead += len;
-                    else if (op != 5u) in_lead = false;
+    const uint32_t shift = kLayout ? layout_shift(first) : 0u;
+    const uint32_t slots = kLayout ? layout_slots(first, cnt) : cnt;
+    if (kLayout) {
+        if (threadIdx.x == 0) s_set = 0u;
+        __syncthreads();
+    }
+    for (uint32_t s0 = 0; s0 < slots; s0 += 256u) {          // uniform
+        const uint32_t slot = s0 + threadIdx.x;
+        const bool active = kLayout ? layout_slot_active(first, cnt, slot) : slot < cnt;
+        bool mate = false, run = false, in_set = false;
+        if (active) {
+            const uint32_t i = slot - shift;
+            const uint8_t* rec = base + o[i];
+            uint32_t f[9];
+            bam_fixed_fields(rec, f);
+            const uint32_t mapq = (f[3] >> 8) & 0xffu, flag = f[4] >> 16, l_seq = f[5];
+            const int64_t r = first + (int64_t)i;
+            col.tid[r] = (int32_t)f[1];
+            col.pos[r] = (int32_t)f[2];
+            col.mapq[r] = (uint8_t)mapq;
+            col.flag[r] = (uint16_t)flag;
+            col.mtid[r] = (int32_t)f[6];
+            col.mpos[r] = (int32_t)f[7];
+            col.tlen[r] = (int32_t)f[8];
+            long long q_aln = 0, ref_len = 0;
+            if (!bam_record_lens(rec, f, &q_aln, &ref_len)) atomicOr(&flags[0], 1u);   // corrupt record
+            if (q_aln > 65535) {
+                q_aln = 65535;
+                atomicAdd(&flags[1], 1u);                    // saturated qlen
+            }
+            col.qlen[r] = (uint16_t)q_aln;
+            const int64_t rel = rel_base + (int64_t)rec_base[b] + (int64_t)i;     // index among the records of this call
+            if (rel < head_records) {
+                col.head_rlen[rel] = (int32_t)l_seq;
+                col.head_alen[rel] = (int32_t)ref_len;
+                col.head_qlen[rel] = (uint16_t)q_aln;
+            }
+            if (kLayout) {
+                const int32_t tid = (int32_t)f[1], mtid = (int32_t)f[6];
+                mate = layout_mate_elsewhere(tid, mtid);
+                in_set = lay.set && layout_in_set(tid, mtid, flag, lay.n_refs);
+                // the reference of the record before: the offset before in this block, or the last record of the nearest
+                // earlier block that a record begins in (block 0 is the tail slot)
+                if (i > 0u) {
+                    run = (int32_t)ld32u(base + o[i - 1u] + 4) != tid;
+                } else {
+                    uint32_t pb = b;
+                    while (pb > 0u && count[pb - 1u] == 0u) --pb;
+                    if (pb > 0u) {
+                        --pb;
+                        const uint8_t* pbase = inflated + (size_t)blocks[pb].dst_off_lo + ((size_t)blocks[pb].dst_off_hi << 32);
+                        run = (int32_t)ld32u(pbase + offs[(size_t)pb * kBamBlockRecs + count[pb] - 1u] + 4) != tid;
+                    }
                 }
             }
-            for (uint32_t c = n_cigar; c-- > 1u;) {
-                const uint32_t v = ld32u(cg + 4u * c);
-                const uint32_t op = v & 15u, len = v >> 4;
-                if (op == 4u) trail += len;
-                else if (op != 5u) break;
+        }
+        if (kLayout) {
+            const unsigned long long m_mate = __ballot(mate), m_run = __ballot(run), m_set = __ballot(in_set);
+            const uint32_t lane = threadIdx.x & 63u;
+            if ((lane & 31u) == 0u) {
+                const int64_t word_first = layout_word_first(first, slot);
+                if (layout_word_touched(word_first, first, cnt)) {
+                    const bool whole = layout_word_whole(word_first, first, cnt);
+                    const uint32_t sh = lane;               // 0 or 32
+                    plane_put(lay.mate, word_first, (uint32_t)(m_mate >> sh), whole);
+                    plane_put(lay.runs, word_first, (uint32_t)(m_run >> sh), whole);
+                    if (lay.set) {
+                        const uint32_t bits = (uint32_t)(m_set >> sh);
+                        plane_put(lay.set, word_first, bits, whole);
+                        if (bits) atomicAdd(&s_set, (uint32_t)__popc(bits));
+                    }
+                }
             }
         }
-        long long q_aln = (l_seq ? (long long)l_seq : q_total) - lead - trail;
-        if (q_aln < 0) q_aln = 0;
-        if (q_aln > 65535) {
-            q_aln = 65535;
-            atomicAdd(&flags[1], 1u);                        // saturated qlen
-        }
-        col.qlen[r] = (uint16_t)q_aln;
-        const int64_t rel = rel_base + (int64_t)rec_base[b] + (int64_t)i;     // index among the records of this call
-        if (rel < head_records) {
-            col.head_rlen[rel] = (int32_t)l_seq;
-            col.head_alen[rel] = (int32_t)ref_len;
-            col.head_qlen[rel] = (uint16_t)q_aln;
-        }
     }
+    if (kLayout && lay.set) {
+        __syncthreads();
+        if (threadIdx.x == 0) lay.set_count[b] = s_set;
+    }
+}
+
+// The set counts of a chunk's blocks -> where each block's entries begin: an exclusive scan from the running total in
+// state[1], which goes on by the chunk's sum.  One workgroup; chunk j's runs behind chunk j - 1's (an event between the
+// slots' streams).  state[0]: the entries no longer fit the columns (cap; one more than there are must).
+__global__ __launch_bounds__(256) void bam_entry_scan_kernel(const uint32_t* __restrict__ set_count, uint32_t n_blocks,
+                                                             uint32_t* __restrict__ ent_base, uint32_t* __restrict__ state, uint32_t cap) {
+    __shared__ uint32_t s_w[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint32_t per = (n_blocks + 255u) / 256u;
+    const uint32_t b0 = (uint32_t)t * per < n_blocks ? (uint32_t)t * per : n_blocks, b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
+    uint32_t sum = 0;
+    for (uint32_t b = b0; b < b1; ++b) sum += set_count[b];
+    uint32_t x = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t v = (uint32_t)__shfl_up((int)x, d, 64);
+        if (lane >= d) x += v;
+    }
+    if (lane == 63) s_w[wave] = x;
+    __syncthreads();
+    const uint32_t before = state[1];
+    uint32_t off = before + x - sum, total = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (q < wave) off += s_w[q];
+        total += s_w[q];
+    }
+    for (uint32_t b = b0; b < b1; ++b) {
+        ent_base[b] = off;
+        off += set_count[b];
+    }
+    __syncthreads();                                         // (every thread has read state[1])
+    if (t == 0) {
+        state[1] = before + total;
+        if ((unsigned long long)before + total + 1ull > (unsigned long long)cap) state[0] = 1u;
+    }
+}
+
+// The entries of a chunk's set records, in record order, from the inflated bytes: one workgroup per block, a thread per
+// record, 256 records a turn - a record's entry position is the block's base + the set records before it.  The lane that
+// holds the first record of a 16 384-record block writes that block's offset.  Nothing is written at or behind `cap`.
+__global__ __launch_bounds__(256) void bam_entries_kernel(const uint8_t* __restrict__ inflated, const BgzfBlock* __restrict__ blocks,
+                                                          const uint16_t* __restrict__ offs, const uint32_t* __restrict__ count,
+                                                          const uint32_t* __restrict__ rec_base, int64_t out_base, BamLayout lay) {
+    __shared__ uint32_t s_w[2][4];
+    const uint32_t b = blockIdx.x;
+    const uint32_t cnt = count[b];
+    const uint8_t* base = inflated + (size_t)blocks[b].dst_off_lo + ((size_t)blocks[b].dst_off_hi << 32);
+    const uint16_t* o = offs + (size_t)b * kBamBlockRecs;
+    const int64_t first = out_base + (int64_t)rec_base[b];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t running = lay.ent_base[b];
+    uint32_t turn = 0;
+    for (uint32_t i0 = 0; i0 < cnt; i0 += 256u, ++turn) {    // uniform
+        const uint32_t i = i0 + threadIdx.x;
+        const bool active = i < cnt;
+        const uint8_t* rec = base;
+        uint32_t f[9] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        bool in_set = false;
+        if (active) {
+            rec = base + o[i];
+            bam_fixed_fields(rec, f);
+            in_set = layout_in_set((int32_t)f[1], (int32_t)f[6], f[4] >> 16, lay.n_refs);
+        }
+        const unsigned long long m = __ballot(in_set);
+        if (lane == 0u) s_w[turn & 1u][wave] = (uint32_t)__popcll(m);
+        __syncthreads();                                     // (two sets of wave counts: one barrier a turn)
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) {
+            const uint32_t c = s_w[turn & 1u][q];
+            if (q < wave) before += c;
+            total += c;
+        }
+        const uint32_t e = running + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        const int64_t r = first + (int64_t)i;
+        if (active && layout_is_border(r)) lay.off[r / kLayoutTile] = e;
+        if (in_set && e < lay.cap) {
+            long long q_aln = 0, ref_len = 0;
+            (void)bam_record_lens(rec, f, &q_aln, &ref_len);
+            if (q_aln > 65535) q_aln = 65535;
+            lay.e_tid[e] = (int32_t)f[1];
+            lay.e_mtid[e] = (int32_t)f[6];
+            lay.e_pos[e] = (int32_t)f[2];
+            lay.e_mpos[e] = (int32_t)f[7];
+            lay.e_fq[e] = (f[4] >> 16) | ((uint32_t)q_aln << 16);
+            lay.e_mapq[e] = (uint8_t)((f[3] >> 8) & 0xffu);
+        }
+        running += total;
+    }
+}
+
+// What no chunk could write alone, when every chunk has been decoded: the run bit of each chunk's first record (`seams`:
+// their record indices; record 0 gets 1, every other is compared with the record before it in the `tid` column - two
+// values per chunk, not a pass), and the stream's last offset.
+struct LayoutSeams { int64_t at[48]; int32_t n; };
+__global__ __launch_bounds__(64) void bam_layout_seams_kernel(LayoutSeams seams, const int32_t* __restrict__ tid, int64_t n_records,
+                                                              uint32_t* __restrict__ runs, uint32_t* __restrict__ off,
+                                                              const uint32_t* __restrict__ state) {
+    const int t = threadIdx.x;
+    if (t < seams.n) {
+        const int64_t r = seams.at[t];
+        if (r >= 0 && r < n_records && (r == 0 || tid[r] != tid[r - 1])) atomicOr(runs + (r >> 5), 1u << (uint32_t)(r & 31));
+    }
+    if (t == 63 && off) off[(n_records + (int64_t)kLayoutTile - 1) / kLayoutTile] = state[1];
+}
+
+// the bits at and behind record n of the byte that holds it, in three planes (the bytes behind it: a memset)
+__global__ __launch_bounds__(64) void plane_clear_tail_kernel(uint8_t* p0, uint8_t* p1, uint8_t* p2, int64_t n) {
+    uint8_t* p = threadIdx.x == 0 ? p0 : threadIdx.x == 1 ? p1 : threadIdx.x == 2 ? p2 : nullptr;
+    if (p) p[n >> 3] &= (uint8_t)((1u << (uint32_t)(n & 7)) - 1u);
 }
 
 int launch_bgzf_inflate(hipStream_t s, const uint8_t* src, const BgzfBlock* blocks, uint32_t n_blocks, uint8_t* dst,
@@ -1651,11 +1842,52 @@ int launch_bam_walk_scan(hipStream_t s, const uint8_t* inflated, const BgzfBlock
 
 int launch_bam_decode(hipStream_t s, const uint8_t* inflated, const BgzfBlock* blocks, uint32_t n_blocks, const uint16_t* offs,
                       const uint32_t* count, const uint32_t* rec_base, const BamColumns& col, int64_t out_base,
-                      int64_t rel_base, int64_t head_records, uint32_t* flags) {
+                      int64_t rel_base, int64_t head_records, uint32_t* flags, const BamLayout* lay) {
     if (n_blocks == 0) return BESST_OK;
-    hipLaunchKernelGGL(bam_decode_kernel, dim3(n_blocks), dim3(256), 0, s, inflated, blocks, offs, count, rec_base, col, out_base,
-                       rel_base, head_records, flags);
+    if (lay)
+        hipLaunchKernelGGL(bam_decode_kernel<true>, dim3(n_blocks), dim3(256), 0, s, inflated, blocks, offs, count, rec_base, col, out_base,
+                           rel_base, head_records, flags, *lay);
+    else
+        hipLaunchKernelGGL(bam_decode_kernel<false>, dim3(n_blocks), dim3(256), 0, s, inflated, blocks, offs, count, rec_base, col, out_base,
+                           rel_base, head_records, flags, BamLayout{});
     BESST_HIP_TRY(hipGetLastError());
+    return BESST_OK;
+}
+
+int launch_bam_entry_scan(hipStream_t s, uint32_t n_blocks, const BamLayout& lay) {
+    if (n_blocks == 0) return BESST_OK;
+    hipLaunchKernelGGL(bam_entry_scan_kernel, dim3(1), dim3(256), 0, s, lay.set_count, n_blocks, lay.ent_base, lay.state, lay.cap);
+    BESST_HIP_TRY(hipGetLastError());
+    return BESST_OK;
+}
+
+int launch_bam_entries(hipStream_t s, const uint8_t* inflated, const BgzfBlock* blocks, uint32_t n_blocks, const uint16_t* offs,
+                       const uint32_t* count, const uint32_t* rec_base, int64_t out_base, const BamLayout& lay) {
+    if (n_blocks == 0) return BESST_OK;
+    hipLaunchKernelGGL(bam_entries_kernel, dim3(n_blocks), dim3(256), 0, s, inflated, blocks, offs, count, rec_base, out_base, lay);
+    BESST_HIP_TRY(hipGetLastError());
+    return BESST_OK;
+}
+
+int launch_bam_layout_seams(hipStream_t s, const int64_t* seams, size_t n_seams, const int32_t* tid, int64_t n_records, uint32_t* runs,
+                            uint32_t* off, const uint32_t* state) {
+    for (size_t at = 0; at < n_seams || at == 0; at += 48) {
+        LayoutSeams batch{};
+        for (; batch.n < 48 && at + (size_t)batch.n < n_seams; ++batch.n) batch.at[batch.n] = seams[at + (size_t)batch.n];
+        hipLaunchKernelGGL(bam_layout_seams_kernel, dim3(1), dim3(64), 0, s, batch, tid, n_records, runs, at == 0 ? off : nullptr, state);
+    }
+    BESST_HIP_TRY(hipGetLastError());
+    return BESST_OK;
+}
+
+int launch_plane_clear_from(hipStream_t s, uint8_t* const planes[3], const size_t cap_bytes[3], int64_t n_records) {
+    const size_t byte = (size_t)(n_records >> 3);
+    for (int k = 0; k < 3; ++k)
+        if (planes[k] && byte >= cap_bytes[k]) { set_error("ingest layout: a bit plane is shorter than the records it describes"); return BESST_ERR_STATE; }
+    hipLaunchKernelGGL(plane_clear_tail_kernel, dim3(1), dim3(64), 0, s, planes[0], planes[1], planes[2], n_records);
+    BESST_HIP_TRY(hipGetLastError());
+    for (int k = 0; k < 3; ++k)
+        if (planes[k] && cap_bytes[k] > byte + 1) BESST_HIP_TRY(hipMemsetAsync(planes[k] + byte + 1, 0, cap_bytes[k] - byte - 1, s));
     return BESST_OK;
 }
 

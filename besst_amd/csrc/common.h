@@ -66,9 +66,33 @@ constexpr uint32_t kWalkFirstGuessed = 1u, kWalkOverhang = 2u;
 int launch_bam_walk_scan(hipStream_t s, const uint8_t* inflated, const BgzfBlock* blocks, uint32_t n_blocks, uint64_t chunk_end,
                          int32_t n_ref, uint32_t forced_block, uint32_t forced_entry, uint32_t mode, const uint32_t* status, uint16_t* offs,
                          uint32_t* count, uint32_t* exits, uint32_t* rec_base, uint32_t* guess, uint32_t* tail_at, uint32_t* summary);
+// What a chunk's decode leaves beside the columns (ingest_layout_core.h has the rules): the three bit planes as words -
+// set == nullptr: the two of besst_dev_record_bits only -, and for the candidate side stream two words per BGZF block of
+// the chunk (set_count, ent_base), the running state (state[0]: the entries did not fit, state[1]: entries so far), the
+// offsets and the six entry columns of `cap` entries each.
+struct BamLayout {
+    uint32_t *mate, *runs, *set;
+    uint32_t *set_count, *ent_base, *state, *off;
+    int32_t *e_tid, *e_mtid, *e_pos, *e_mpos;
+    uint32_t* e_fq;
+    uint8_t* e_mapq;
+    uint32_t cap, n_refs;
+};
+// lay == nullptr: the columns alone
 int launch_bam_decode(hipStream_t s, const uint8_t* inflated, const BgzfBlock* blocks, uint32_t n_blocks, const uint16_t* offs,
                       const uint32_t* count, const uint32_t* rec_base, const BamColumns& col, int64_t out_base,
-                      int64_t rel_base, int64_t head_records, uint32_t* flags);
+                      int64_t rel_base, int64_t head_records, uint32_t* flags, const BamLayout* lay = nullptr);
+// behind a chunk's decode, for lay.set != nullptr: the blocks' entry positions (one workgroup; ordered behind the chunk
+// before by the caller), then the entries and the offsets of the 16 384-record borders inside the chunk
+int launch_bam_entry_scan(hipStream_t s, uint32_t n_blocks, const BamLayout& lay);
+int launch_bam_entries(hipStream_t s, const uint8_t* inflated, const BgzfBlock* blocks, uint32_t n_blocks, const uint16_t* offs,
+                       const uint32_t* count, const uint32_t* rec_base, int64_t out_base, const BamLayout& lay);
+// when every chunk is decoded: the run bits of the chunks' first records (`seams`: their record indices, host memory)
+// and, with off != nullptr, the stream's last offset
+int launch_bam_layout_seams(hipStream_t s, const int64_t* seams, size_t n_seams, const int32_t* tid, int64_t n_records, uint32_t* runs,
+                            uint32_t* off, const uint32_t* state);
+// zeroes every bit at and behind record n_records in up to three planes of cap_bytes[k] bytes (nullptr: none)
+int launch_plane_clear_from(hipStream_t s, uint8_t* const planes[3], const size_t cap_bytes[3], int64_t n_records);
 
 // ---- per-kernel timing (HIP events on the launch stream; off unless besst_prof_enable(1)) ----------
 enum ProfSlot {

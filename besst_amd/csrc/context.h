@@ -64,6 +64,9 @@ struct besst_ctx {
     besst_cand_stream cs{};
     int64_t cs_upto = 0;
     int64_t cs_cap_entries = 0;             // entries a column of cs_entries holds (the columns' stride)
+    // (a device ingest - ingest.hip - writes the planes and the stream while it decodes and moves the three watermarks
+    // itself; a build then finds nothing to make)
+    int64_t maker_launches = 0;             // launches of the planes' and the stream's makers by besst_ctx_build_graph
     // tuple stream + edge table
     besst::DevBuf<uint64_t> keys, payload, row_key;
     besst::DevBuf<uint32_t> row_mask, row_n, row_first, row_offset;

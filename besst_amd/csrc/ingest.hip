@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "context.h"
+#include "ingest_layout_core.h"
 
 using namespace besst;
 
@@ -116,6 +117,66 @@ int64_t column_room(int64_t resident, int64_t pushed, int64_t read_bytes, int64_
     if (want < need) want = need;
     if (want >= ((int64_t)1 << 32)) want = ((int64_t)1 << 32) - 1;
     return want;
+}
+
+// ---- the layout a device ingest leaves beside the columns: its buffers ---------------------------------------------------
+// A plane / the offsets with room for `want` elements: the first `keep` carried over, everything behind them zero (the
+// planes are ORed into).
+template <class T>
+int regrow_zeroed(besst_ctx* c, DevBuf<T>& buf, size_t keep, size_t want) {
+    if (want <= buf.cap) return BESST_OK;
+    DevBuf<T> bigger;
+    int rc = bigger.ensure(want);
+    if (rc) return rc;
+    if (keep > buf.cap) keep = buf.cap;
+    hipError_t e = hipMemsetAsync(bigger.p, 0, bigger.cap * sizeof(T), c->stream);
+    if (e == hipSuccess && keep) e = hipMemcpyAsync(bigger.p, buf.p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        bigger.release();
+        set_error("push_bam_device: %s", hipGetErrorString(e));
+        return BESST_ERR_HIP;
+    }
+    buf.release();
+    buf = bigger;
+    return BESST_OK;
+}
+
+// the context's stream descriptor points at the buffers where they lie now (counts and n_refs stay)
+void point_stream(besst_ctx* c) {
+    const size_t cap = (size_t)c->cs_cap_entries;
+    char* e = reinterpret_cast<char*>(c->cs_entries.p);
+    c->cs.offsets = c->cs_off.p;
+    c->cs.set_bits = c->cs_set.p;
+    c->cs.tid = e; c->cs.mtid = e + cap * 4; c->cs.pos = e + cap * 8; c->cs.mpos = e + cap * 12;
+    c->cs.flag_qlen = e + cap * 16; c->cs.mapq = e + cap * 20;
+}
+
+// The six entry columns carved anew for `cap` entries each (a multiple of 64), the first `valid` entries of every column
+// carried over to the new stride.
+int carve_entries(besst_ctx* c, int64_t cap, int64_t valid) {
+    uint8_t* p = nullptr;
+    if (hipMalloc((void**)&p, (size_t)cap * 21) != hipSuccess) {
+        set_error("push_bam_device: cannot allocate %zu bytes for the candidate entries", (size_t)cap * 21);
+        return BESST_ERR_NOMEM;
+    }
+    const size_t old = (size_t)c->cs_cap_entries;
+    static const size_t at[6] = {0, 4, 8, 12, 16, 20}, width[6] = {4, 4, 4, 4, 4, 1};
+    hipError_t e = hipSuccess;
+    if (valid > (int64_t)old) valid = (int64_t)old;
+    for (int k = 0; k < 6 && e == hipSuccess && valid > 0; ++k)
+        e = hipMemcpyAsync(p + (size_t)cap * at[k], c->cs_entries.p + old * at[k], (size_t)valid * width[k], hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        set_error("push_bam_device: %s", hipGetErrorString(e));
+        return BESST_ERR_HIP;
+    }
+    c->cs_entries.release();
+    c->cs_entries.p = p;
+    c->cs_entries.cap = (size_t)cap * 21;
+    c->cs_cap_entries = cap;
+    return BESST_OK;
 }
 
 }  // namespace
@@ -245,9 +306,9 @@ namespace {
 
 constexpr int kSlots = 3;            // chunk j's starts being verified, j + 1 inflating, j + 2 on its way to the device
 constexpr size_t kTailRoom = kBgzfTailRoom;
-enum SlotEvent { kH2dDone = 0, kSlotFree, kSummDone, kTailTaken, kSlotEvents };
+enum SlotEvent { kH2dDone = 0, kSlotFree, kSummDone, kTailTaken, kScanDone, kSlotEvents };
 
-// What every device ingest needs whatever the file: four streams (4 ms each to create: 17 of a call's 18 ms of set-up), twelve
+// What every device ingest needs whatever the file: four streams (4 ms each to create: 17 of a call's 18 ms of set-up), fifteen
 // events and three small buffers.  One set per device stays with the process; a call takes it (a second call on the same
 // device at the same time makes its own and destroys it), besst_release_cached_memory() does not touch it (a few KB).
 struct IngestHandles {
@@ -255,8 +316,8 @@ struct IngestHandles {
     hipEvent_t ev[kSlots][kSlotEvents] = {};
     char* heads = nullptr;           // head_rlen | head_alen | head_qlen on the device
     size_t heads_bytes = 0;
-    uint32_t* d_flags = nullptr;     // corrupt-record bit, saturated-qlen count
-    uint32_t* summ_host = nullptr;   // pinned: kSlots x 12 summary words | [40] [41] flag words | [48..] kSlots tail descriptors
+    uint32_t* d_flags = nullptr;     // corrupt-record bit, saturated-qlen count | the layout's state: entries did not fit, entries so far
+    uint32_t* summ_host = nullptr;   // pinned: kSlots x 12 summary words | [40] .. [43] flag words | [44] entries before the call | [45] entries so far, read where the columns grow | [48..] kSlots tail descriptors
 };
 struct IngestKit {
     std::mutex mu;
@@ -265,7 +326,7 @@ struct IngestKit {
 };
 IngestKit g_ingest_kit[16];
 
-// a work stream at `priority` and the four events of its slot, where they are missing
+// a work stream at `priority` and the five events of its slot, where they are missing
 bool make_slot_handles(hipStream_t* work, hipEvent_t* ev, int priority) {
     if (!*work && hipStreamCreateWithPriority(work, hipStreamNonBlocking, priority) != hipSuccess) return false;
     for (int i = 0; i < kSlotEvents; ++i)
@@ -295,7 +356,7 @@ struct Slot {
     uint8_t* inflated = nullptr;
     uint32_t* symbols = nullptr; // the inflate kernel's symbol buffer: four bytes per byte of `inflated` (touched: per symbol)
     uint16_t* offs = nullptr;
-    uint32_t* words = nullptr;   // status | count | exits | rec_base | guess | tail_at (nbw each), then 8 summary words
+    uint32_t* words = nullptr;   // status | count | exits | rec_base | guess | tail_at (nbw each), 12 summary words, then set_count | ent_base (nbw each)
     Chunk ck;
 };
 
@@ -334,6 +395,16 @@ struct DeviceIngest {
     // the slice form's answers
     int64_t first_at = -1, carry_out = 0, over_bytes = 0;
     int64_t no_start_left = -1;      // >= 0: a slice no record begins in; so many bytes of the record before lie behind it
+    // The layout step (BESST_INGEST_LAYOUT=0: none of it): the decode writes the mate-elsewhere and run planes, and the set
+    // plane, the offsets and the entries of the candidate side stream - each only where the context's own watermark stands
+    // at its last record, so that what the call writes continues what is valid (else the next build extends it as ever).
+    bool lay_planes = false, lay_stream = false;
+    int64_t cap_before = 0;          // entries the columns held room for when the call began (a failed call puts that back)
+    int64_t cap_limit = INT64_MAX;   // BESST_INGEST_ENTRY_ROOM: the kernels take the columns for no longer than this until they are carved by share
+    bool stream_began = false;       // lay_stream when the call began (it is given up where its buffers cannot be allocated)
+    int64_t entries_before = 0;      // entries of the records that were resident
+    int64_t entry_room = -1;         // BESST_INGEST_ENTRY_ROOM: entries the columns are first carved for (< 0: the default share)
+    std::vector<int64_t> seams;      // record index of every chunk's first record
 
     DeviceIngest(besst_ctx* c_, besst_bam* bam_, int32_t part_, int32_t parts_, int64_t head_records_, int64_t first_skip_, bool slice_)
         : c(c_), bam(bam_), part(part_), parts(parts_), head_records(head_records_), first_skip(first_skip_), slice(slice_) {}
@@ -354,7 +425,7 @@ struct DeviceIngest {
              hipMalloc((void**)&q.dev, plan.slot_bytes) == hipSuccess && hipMalloc((void**)&q.inflated, plan.inflated_cap) == hipSuccess &&
              hipMalloc((void**)&q.symbols, 4 * bgzf_inflate_symbol_places(plan.inflated_cap, plan.nbw)) == hipSuccess &&
              hipMalloc((void**)&q.offs, plan.nbw * (size_t)kBamBlockRecs * sizeof(uint16_t)) == hipSuccess &&
-             hipMalloc((void**)&q.words, (plan.nbw * 6 + 12) * sizeof(uint32_t)) == hipSuccess;
+             hipMalloc((void**)&q.words, (plan.nbw * 8 + 12) * sizeof(uint32_t)) == hipSuccess;
         alloc_s += seconds_since(t0);
         return got;
     }
@@ -375,7 +446,7 @@ struct DeviceIngest {
     // streams before, 1.40 in one that had not.  So the slots' streams are created at the LOWEST priority, a level nobody
     // else in the process uses (its queues are theirs alone; nothing else runs during an ingest for them to yield to), and
     // the copy stream at the highest - the slots' first, in slot order: the queue placement depends on it.
-    // Every slot's stream AND its four events are made here, on the calling thread, before anything is queued: the helper
+    // Every slot's stream AND its five events are made here, on the calling thread, before anything is queued: the helper
     // only allocates memory, so no handle the queueing code reads - slot 2's tail_taken while chunk 0 is enqueued - is ever
     // written beside it.
     bool take_handles() {
@@ -401,7 +472,7 @@ struct DeviceIngest {
             if (hipMalloc((void**)&h.heads, head_n * 10) != hipSuccess) return false;
             h.heads_bytes = head_n * 10;
         }
-        return (h.d_flags || hipMalloc((void**)&h.d_flags, 2 * sizeof(uint32_t)) == hipSuccess) &&
+        return (h.d_flags || hipMalloc((void**)&h.d_flags, 4 * sizeof(uint32_t)) == hipSuccess) &&
                (h.summ_host || hipHostMalloc((void**)&h.summ_host, 128 * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess) &&
                (h.copy || hipStreamCreateWithPriority(&h.copy, hipStreamNonBlocking, prio_high) == hipSuccess);
     }
@@ -455,6 +526,80 @@ struct DeviceIngest {
         else drop();
     }
 
+    // Which parts of the layout this call continues, read at every call like the other switches.
+    void plan_layout() {
+        const char* sw = getenv("BESST_INGEST_LAYOUT");
+        const bool on = !(sw && sw[0] == '0' && sw[1] == 0);
+        lay_planes = on && c->bits_upto == c->n_records && c->tid_bits_upto == c->n_records;
+        lay_stream = lay_planes && c->cs_upto == c->n_records && (c->n_records == 0 || c->cs.n_refs == (int64_t)n_ref);
+        stream_began = lay_stream;
+        cap_before = c->cs_cap_entries;
+        entries_before = lay_stream && c->n_records > 0 ? c->cs.n_entries : 0;
+        if (const char* e = getenv("BESST_INGEST_ENTRY_ROOM"); e && e[0]) entry_room = atoll(e) < 0 ? 0 : atoll(e);
+    }
+
+    // The planes, the offsets and the entry columns fit the record columns' capacity; `have` records' worth of them is
+    // valid and moves along, the rest of the planes is zero.  Called where the record columns may have grown - every slot
+    // has been waited for there, so the running entry total can be read.
+    // The entry columns' size is known only at the end.  They are carved for what is there plus the room left in the
+    // record columns times the share of records that got an entry so far, plus a quarter (layout_entry_cap), and only
+    // ever grow.  Before a count has come back the share is kLayoutDefaultShare - every record: that first carving cannot
+    // be too small (BESST_INGEST_ENTRY_ROOM replaces it: so many entries).  Behind a growth the rest of the file may hold
+    // more entries per record than its head by more than the margin: entries that do not fit raise the state's flag and
+    // are not written, and the build makes the stream.
+    bool fit_layout(int64_t have) {
+        if (!lay_planes) return true;
+        const size_t room = c->tid.cap > (size_t)have ? c->tid.cap : (size_t)have;
+        const size_t plane_bytes = (room / 8 + 32 + 15) / 16 * 16, keep = (size_t)((have + 7) / 8);
+        if ((rc = regrow_zeroed(c, c->mate_bits, keep, plane_bytes)) || (rc = regrow_zeroed(c, c->tid_bits, keep, plane_bytes))) return false;
+        if (!lay_stream) return true;
+        const bool ok = fit_stream(have, room, keep, plane_bytes);
+        point_stream(c);                                         // (on every way out: a buffer may have moved before another failed)
+        return ok;
+    }
+
+    // the stream's part of fit_layout.  Memory that is not there costs the stream, not the call: the planes go on, cs_upto
+    // stays where it was and the build makes the stream, as after entries that did not fit.
+    bool fit_stream(int64_t have, size_t room, size_t keep, size_t plane_bytes) {
+        auto gave_up = [&](int status) {
+            if (status != BESST_ERR_NOMEM) return false;
+            (void)hipGetLastError();                             // (the failed allocation's error is not the next launch's)
+            lay_stream = false;
+            rc = BESST_OK;
+            return true;
+        };
+        if ((rc = regrow_zeroed(c, c->cs_set, keep, plane_bytes))) return gave_up(rc);
+        const size_t off_keep = have > 0 ? (size_t)((have + kLayoutTile - 1) / kLayoutTile + 1) : 0;
+        if ((rc = regrow_zeroed(c, c->cs_off, off_keep, (room / kLayoutTile + 2 + 3) / 4 * 4))) return gave_up(rc);
+        int64_t total = entries_before;
+        if (pushed > 0) {
+            hipError_t e = hipMemcpyAsync(h.summ_host + 45, h.d_flags + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) { hip_fail(e); return false; }
+            total = (int64_t)h.summ_host[45];
+        }
+        int64_t want;
+        if (pushed == 0 && entry_room >= 0) {
+            want = (total + entry_room + 1 + 63) / 64 * 64;
+            cap_limit = want;                                    // (columns that hold more from an earlier call count as this long)
+        } else {
+            cap_limit = INT64_MAX;
+            const double share = pushed > 0 ? (double)(total - entries_before) / (double)pushed : kLayoutDefaultShare;
+            want = layout_entry_cap(total, (int64_t)room - have, share);
+        }
+        if (want > c->cs_cap_entries && (rc = carve_entries(c, want, total))) return gave_up(rc);
+        return true;
+    }
+
+    // every plane bit at and behind the context's last record is 0 (before the first decode, and again after a call that
+    // failed: the planes are ORed into, and the next call must find zeros)
+    bool clear_planes() {
+        if (!lay_planes) return true;
+        uint8_t* const planes[3] = {c->mate_bits.p, c->tid_bits.p, stream_began ? c->cs_set.p : nullptr};
+        const size_t caps[3] = {c->mate_bits.cap, c->tid_bits.cap, c->cs_set.cap};
+        return launch_plane_clear_from(c->stream, planes, caps, c->n_records) == BESST_OK;
+    }
+
     // The part of the file, its chunks, the handles and slot 0.  false: the call ends here (rc, nothing left allocated).
     bool setup(int64_t chunk_blocks) {
         int64_t at = 0;
@@ -471,6 +616,8 @@ struct DeviceIngest {
         plan = plan_bgzf_chunks(bam_file_map(bam), map_len, f0, (size_t)chunk_blocks);
         head_n = (size_t)(head_records > 0 ? head_records : 1);
         n_ref = besst_bam_n_references(bam);
+        plan_layout();
+        if (!fit_layout(c->n_records)) return false;             // (rc is set; nothing of the call's is allocated yet)
         // Slot 0 now; slots 1 and 2 - 2 x (~190 MB pinned + ~0.7 GB of HBM): 90 of the 130 ms a first ingest spent allocating -
         // on a helper thread while the first chunk is read, uploaded and queued (joined before the second chunk is staged, and
         // before anything is released).
@@ -494,8 +641,13 @@ struct DeviceIngest {
         col.head_rlen = reinterpret_cast<int32_t*>(h.heads);
         col.head_alen = reinterpret_cast<int32_t*>(h.heads + head_n * 4);
         col.head_qlen = reinterpret_cast<uint16_t*>(h.heads + head_n * 8);
-        hipError_t e = hipMemsetAsync(h.d_flags, 0, 2 * sizeof(uint32_t), c->stream);
+        hipError_t e = hipMemsetAsync(h.d_flags, 0, 4 * sizeof(uint32_t), c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(h.heads, 0, head_n * 10, c->stream);
+        if (e == hipSuccess && entries_before) {                 // the running entry total goes on from the resident stream's
+            h.summ_host[44] = (uint32_t)entries_before;
+            e = hipMemcpyAsync(h.d_flags + 3, h.summ_host + 44, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+        }
+        if (e == hipSuccess && !clear_planes()) rc = BESST_ERR_HIP;
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the slots' streams start behind these
         if (e != hipSuccess) hip_fail(e);
         setup_s = seconds_since(t_start);
@@ -716,7 +868,7 @@ struct DeviceIngest {
         for (int k = 0; k < kSlots && e == hipSuccess; ++k) e = hipEventSynchronize(h.ev[k][kSlotFree]);   // (behind a slot's last decode)
         wait_s += seconds_since(t0);
         if (e != hipSuccess) { hip_fail(e); return false; }
-        return (rc = reserve_records(c, have, want)) == BESST_OK;
+        return (rc = reserve_records(c, have, want)) == BESST_OK && fit_layout(have);
     }
 
     // The pipeline: while the host waits for chunk j's summary, chunk j + 1 inflates and chunk j + 2 is read, uploaded and
@@ -746,8 +898,39 @@ struct DeviceIngest {
             if (!grow_columns(j, have, have + got)) break;
             col.tid = c->tid.p; col.mtid = c->mtid.p; col.pos = c->pos.p; col.mpos = c->mpos.p; col.tlen = c->tlen.p;
             col.flag = c->flag.p; col.qlen = c->qlen.p; col.mapq = c->mapq.p;
-            if (launch_bam_decode(h.work[k], q.inflated, reinterpret_cast<const BgzfBlock*>(q.dev), q.ck.n_blocks + 1, q.offs, q.words + plan.nbw,
-                                  q.words + 3 * plan.nbw, col, have, pushed, head_records, h.d_flags)) { rc = BESST_ERR_HIP; break; }
+            BamLayout lay{};
+            if (lay_planes) {
+                lay.mate = reinterpret_cast<uint32_t*>(c->mate_bits.p);
+                lay.runs = reinterpret_cast<uint32_t*>(c->tid_bits.p);
+                lay.n_refs = (uint32_t)n_ref;
+                seams.push_back(have);
+            }
+            if (lay_stream) {
+                char* ent = reinterpret_cast<char*>(c->cs_entries.p);
+                const size_t cap = (size_t)c->cs_cap_entries;
+                lay.set = reinterpret_cast<uint32_t*>(c->cs_set.p);
+                lay.set_count = q.words + 6 * plan.nbw + 12;
+                lay.ent_base = q.words + 7 * plan.nbw + 12;
+                lay.state = h.d_flags + 2;
+                lay.off = c->cs_off.p;
+                lay.e_tid = reinterpret_cast<int32_t*>(ent); lay.e_mtid = reinterpret_cast<int32_t*>(ent + cap * 4);
+                lay.e_pos = reinterpret_cast<int32_t*>(ent + cap * 8); lay.e_mpos = reinterpret_cast<int32_t*>(ent + cap * 12);
+                lay.e_fq = reinterpret_cast<uint32_t*>(ent + cap * 16); lay.e_mapq = reinterpret_cast<uint8_t*>(ent + cap * 20);
+                lay.cap = (uint32_t)((int64_t)cap < cap_limit ? (int64_t)cap : cap_limit);
+            }
+            const BgzfBlock* desc = reinterpret_cast<const BgzfBlock*>(q.dev);
+            if (launch_bam_decode(h.work[k], q.inflated, desc, q.ck.n_blocks + 1, q.offs, q.words + plan.nbw,
+                                  q.words + 3 * plan.nbw, col, have, pushed, head_records, h.d_flags, lay_planes ? &lay : nullptr)) { rc = BESST_ERR_HIP; break; }
+            if (lay_stream) {
+                // the chunk's entries go on where the chunk before stopped: its scan waits for that one's on the device,
+                // the host for neither
+                if (chunks > 0) e = hipStreamWaitEvent(h.work[k], h.ev[(k + kSlots - 1) % kSlots][kScanDone], 0);
+                if (e != hipSuccess) { hip_fail(e); break; }
+                if (launch_bam_entry_scan(h.work[k], q.ck.n_blocks + 1, lay)) { rc = BESST_ERR_HIP; break; }
+                e = hipEventRecord(h.ev[k][kScanDone], h.work[k]);
+                if (e != hipSuccess) { hip_fail(e); break; }
+                if (launch_bam_entries(h.work[k], q.inflated, desc, q.ck.n_blocks + 1, q.offs, q.words + plan.nbw, q.words + 3 * plan.nbw, have, lay)) { rc = BESST_ERR_HIP; break; }
+            }
             e = hipEventRecord(h.ev[k][kSlotFree], h.work[k]);
             if (e != hipSuccess) { hip_fail(e); break; }
             pushed += got;
@@ -766,8 +949,13 @@ struct DeviceIngest {
         }
         const hipError_t ec = hipStreamSynchronize(h.copy);
         if (rc == BESST_OK && (e0 != hipSuccess || ec != hipSuccess)) hip_fail(e0 != hipSuccess ? e0 : ec);
+        const int64_t n_new = c->n_records + pushed;
+        if (rc == BESST_OK && lay_planes && pushed > 0 &&
+            launch_bam_layout_seams(c->stream, seams.data(), seams.size(), c->tid.p, n_new, reinterpret_cast<uint32_t*>(c->tid_bits.p),
+                                    lay_stream ? c->cs_off.p : nullptr, h.d_flags + 2))
+            rc = BESST_ERR_HIP;
         if (rc == BESST_OK) {
-            hipError_t e = hipMemcpyAsync(h.summ_host + 40, h.d_flags, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+            hipError_t e = hipMemcpyAsync(h.summ_host + 40, h.d_flags, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
             const int64_t hn = pushed < head_records ? pushed : head_records;
             if (e == hipSuccess && hn > 0) {
                 e = hipMemcpyAsync(head_rlen, col.head_rlen, (size_t)hn * 4, hipMemcpyDeviceToHost, c->stream);
@@ -783,6 +971,39 @@ struct DeviceIngest {
             rc = BESST_ERR_ARG;
         }
         const uint32_t saturated = rc == BESST_OK ? h.summ_host[41] : 0u;
+        const bool entries_fit = rc == BESST_OK && h.summ_host[42] == 0u;
+        const int64_t n_entries = rc == BESST_OK ? (int64_t)h.summ_host[43] : 0;
+        const bool stream_kept = rc == BESST_OK && lay_stream && entries_fit;
+        bool again = false;
+        if (stream_began && !stream_kept && c->n_records > 0) {
+            // the resident stream stays as it was - the call failed, its entries did not fit or its buffers could not be had -,
+            // but the first record of the block behind it has written its own entry position over that stream's last offset:
+            // put it back
+            h.summ_host[44] = (uint32_t)entries_before;
+            (void)hipMemcpyAsync(c->cs_off.p + (c->n_records + kLayoutTile - 1) / kLayoutTile, h.summ_host + 44, sizeof(uint32_t),
+                                 hipMemcpyHostToDevice, c->stream);
+            again = true;
+        }
+        if (rc != BESST_OK && lay_planes) {                      // nothing moves: what the call wrote into the planes goes
+            (void)clear_planes();
+            again = true;
+        }
+        if (again) (void)hipStreamSynchronize(c->stream);
+        if (rc != BESST_OK && stream_began && c->cs_cap_entries != cap_before) {   // ... and the entry columns are as long as they were
+            if (cap_before > 0) {
+                (void)carve_entries(c, cap_before, entries_before);
+            } else {
+                c->cs_entries.release();
+                c->cs_cap_entries = 0;
+            }
+            point_stream(c);
+        }
+        // The first carving took an entry per reserved record; a library with few candidates gives most of that back now
+        // (a copy of the entries there are; a failure leaves the columns as they are).
+        if (stream_kept) {
+            const int64_t fit = layout_entry_cap(n_entries, 0, 0.0);
+            if (c->cs_cap_entries > 2 * fit) (void)carve_entries(c, fit, n_entries);
+        }
         const auto t_rel = Clock::now();
         alloc_join();
         release(rc == BESST_OK);
@@ -790,8 +1011,18 @@ struct DeviceIngest {
             fprintf(stderr, "[push_bam_device] setup %.3f s  alloc %.3f s (%.3f of it waited for)  staging %.3f s  waiting %.3f s  release %.3f s (unpinning %.3f)  total %.3f s\n", setup_s, alloc_s, alloc_wait_s, stage_s,
                     wait_s, seconds_since(t_rel), unpin_s, seconds_since(t_start));
         if (rc) return rc;
-        c->n_records += pushed;
+        c->n_records = n_new;
         c->built = false;
+        if (lay_planes) {                                        // the next build finds nothing to make for these records
+            c->bits_upto = c->tid_bits_upto = n_new;
+            if (stream_kept) {                                   // (else the build makes the stream, as ever)
+                c->cs_upto = n_new;
+                c->cs.n_refs = (int64_t)n_ref;
+                c->cs.n_records = n_new;
+                c->cs.n_entries = n_entries;
+                point_stream(c);
+            }
+        }
         bam_mark_consumed(bam, (int64_t)saturated);
         if (stats) {
             memset(stats, 0, sizeof(*stats));

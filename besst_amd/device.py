@@ -312,6 +312,33 @@ class GraphContext(object):
                    'fetch_records')
         return cols
 
+    LAYOUT_FIELDS = ('n_records', 'bits_upto', 'tid_bits_upto', 'cs_upto', 'n_entries', 'n_refs', 'entry_capacity', 'maker_launches')
+
+    def layout_state(self):
+        """What the context holds of the bit planes and the candidate side stream of its records, and how many maker
+        launches its builds have made (besst_ctx_layout_state) -> dict of LAYOUT_FIELDS.  After a device ingest the three
+        watermarks stand at n_records and the first build launches no maker."""
+        out = np.zeros(8, dtype=np.int64)
+        _lib.check(self._lib.besst_ctx_layout_state(self._ctx, _lib.ptr(out)), 'layout_state')
+        return dict(zip(self.LAYOUT_FIELDS, (int(v) for v in out)))
+
+    def fetch_layout(self):
+        """The valid prefix of the planes and the stream as host arrays (besst_ctx_fetch_layout; tests and tools) -> dict:
+        mate_bits, tid_bits, and - with a stream - set_bits, offsets, n_entries, tid, mtid, pos, mpos, flag_qlen, mapq."""
+        st = self.layout_state()
+        out = dict(mate_bits=np.zeros((st['bits_upto'] + 7) // 8, dtype=np.uint8),
+                   tid_bits=np.zeros((st['tid_bits_upto'] + 7) // 8, dtype=np.uint8))
+        keys = ('set_bits', 'offsets', 'tid', 'mtid', 'pos', 'mpos', 'flag_qlen', 'mapq')
+        if st['cs_upto'] > 0:
+            m = st['n_entries']
+            out.update(set_bits=np.zeros((st['cs_upto'] + 7) // 8, dtype=np.uint8),
+                       offsets=np.zeros((st['cs_upto'] + 16383) // 16384 + 1, dtype=np.uint32), n_entries=m,
+                       tid=np.zeros(m, dtype=np.int32), mtid=np.zeros(m, dtype=np.int32), pos=np.zeros(m, dtype=np.int32),
+                       mpos=np.zeros(m, dtype=np.int32), flag_qlen=np.zeros(m, dtype=np.uint32), mapq=np.zeros(m, dtype=np.uint8))
+        ptrs = [_lib.ptr(out[k]) if k in out and out[k].size else None for k in ('mate_bits', 'tid_bits') + keys]
+        _lib.check(self._lib.besst_ctx_fetch_layout(self._ctx, *ptrs), 'fetch_layout')
+        return out
+
     # ---- library statistics ----------------------------------------------------------------------
     @_timed
     def stream_order(self):

@@ -46,7 +46,8 @@ extern "C" {
  * besst_dev_gzip_plan / besst_dev_gzip_inflate_workspace_bytes / besst_dev_gzip_inflate; the run bits of the record layout besst_dev_record_bits
  * with the trailing member besst_lib_params.tid_bits (see there); the candidate side stream besst_cand_stream with
  * besst_dev_candidate_offsets_bytes / besst_dev_candidate_stream_bytes / besst_dev_candidate_offsets /
- * besst_dev_candidate_stream, the trailing member besst_lib_params.cand_stream, and besst_dev_record_loop_form. */
+ * besst_dev_candidate_stream, the trailing member besst_lib_params.cand_stream, and besst_dev_record_loop_form; the layout
+ * a device ingest leaves beside the columns: besst_ctx_layout_state / besst_ctx_fetch_layout. */
 #define BESST_ABI_VERSION 3
 
 /* status codes */
@@ -290,6 +291,28 @@ int besst_ctx_push_bam_device_part(besst_ctx* ctx, besst_bam* bam, int32_t part,
 int besst_ctx_push_bam_device_slice(besst_ctx* ctx, besst_bam* bam, int32_t part, int32_t parts, int64_t chunk_blocks,
                                     int64_t first_skip, int64_t* boundary, int64_t head_records, int32_t* head_rlen,
                                     int32_t* head_alen, uint16_t* head_qlen, besst_ingest_stats* stats);
+
+/* What a context holds of the ninth to eleventh column groups of its resident records - the mate-elsewhere and run planes
+ * (besst_dev_record_bits) and the candidate side stream (besst_cand_stream) - and who made it.  The three device forms
+ * above write all of it WHILE THEY DECODE, bit for bit what the makers would write from the finished columns (the stream
+ * for n_refs = the file's reference count), and move the watermarks to the last record; besst_ctx_build_graph then
+ * launches no maker and waits for no entry count.  besst_ctx_push_bam and besst_ctx_push_records leave the watermarks
+ * where they are, and the next build extends planes and stream from there.  A device form continues only what stands at
+ * the context's last record when it is called; entries that do not fit the columns reserved for them (sized from the
+ * record reservation: an entry per record at first, the share of records with an entry so far plus a quarter wherever the
+ * record columns grow, cut back to the entries made + 4096 at the end; BESST_INGEST_ENTRY_ROOM=<entries> in the environment
+ * replaces the first), or whose buffers cannot be allocated, leave cs_upto where it was, and the build makes the stream.
+ * BESST_INGEST_LAYOUT=0 in the environment, read at every call: the device forms write the eight columns alone.
+ *   out[0] n_records       out[1] bits_upto: records the mate-elsewhere plane is valid for       out[2] the same, run plane
+ *   out[3] cs_upto: records the side stream is valid for      out[4] its n_entries     out[5] its n_refs  (0 0 without one)
+ *   out[6] entries each entry column has room for
+ *   out[7] maker launches (planes, offsets, entries: one each) by besst_ctx_build_graph since the context was created */
+int besst_ctx_layout_state(besst_ctx* ctx, int64_t* out);
+/* The valid prefix of that layout back on the host, for tests and tools (any pointer may be NULL; the bits behind a
+ * watermark in the byte that holds it come back 0): (bits_upto + 7) / 8 and (tid_bits_upto + 7) / 8 bytes of the two planes; with a stream (cs_upto > 0) (cs_upto + 7) / 8 bytes of the set plane,
+ * ceil(cs_upto / 16384) + 1 offsets and n_entries values of each of the six entry columns. */
+int besst_ctx_fetch_layout(besst_ctx* ctx, uint8_t* mate_bits, uint8_t* tid_bits, uint8_t* set_bits, uint32_t* offsets,
+                           int32_t* tid, int32_t* mtid, int32_t* pos, int32_t* mpos, uint32_t* flag_qlen, uint8_t* mapq);
 
 /* Test hook of the device inflate: the BGZF blocks of `bgzf` (n_bytes, host) inflated on `device`, their output
  * concatenated in out (capacity out_cap, length in *out_len).  BESST_ERR_UNSUPPORTED when a block does not inflate
