@@ -22,7 +22,7 @@ FASTA itself (csrc/fasta.hip: the file's bytes are parsed in HBM by the rules of
 :class:`SequenceRef` handles instead of strings.  A file that begins with the gzip magic is inflated first: a BGZF file
 (what ``--bgzf_outputs`` and ``bgzip`` write) on the device, block by block at its place in the text
 (:func:`_upload_bgzf_file`); any other gzip file by zlib on the host (:func:`_upload_gzip_host`) -
-or, with ``gzip_on_gpu``, a one-member file on the device as well (:func:`_upload_gzip_device`, csrc/gzip_stream.hip).  Like the rest of the package there is no CPU path: without
+or, with ``gzip_on_gpu``, a file of one or of several gzip members on the device as well (:func:`_upload_gzip_device`, csrc/gzip_stream.hip).  Like the rest of the package there is no CPU path: without
 the library or a GPU these calls raise :class:`besst_amd._lib.BesstDeviceError`.
 """
 from __future__ import print_function
@@ -245,14 +245,15 @@ class SequenceStore(object):
         last member that are none, data zlib does not inflate.  The parser's own errors then count bytes of the
         inflated text.
 
-        ``gzip_on_gpu``: a gzip file that is not BGZF - ``gzip``'s own output, one member - is inflated on the device too
-        (:func:`_upload_gzip_device`: block starts found by probing, chunks of ``gzip_chunk_bytes`` compressed bytes
-        decoded against windows that are resolved afterwards); ``inflate`` is then 'device_gzip'.  Whatever the device
-        does not take or finds damaged - several members, an odd header, DEFLATE data, ISIZE or a CRC-32 that is wrong,
-        memory that runs out - is read on the host exactly as without the flag, errors included; ``inflate`` is 'host'
-        then and ``inflate_stats['status']`` names the device's reason.  ``inflate_stats``: chunks, candidates (chunks in
-        which a block start was found), live (chunks that were decoded side by side), text_bytes, status (None: the
-        device's gzip path was not tried).  ``gzip_chunk_bytes``: a multiple of 16 in 256..2^24 (GZIP_CHUNK_BYTES)."""
+        ``gzip_on_gpu``: a gzip file that is not BGZF - ``gzip``'s own output, one member or a series of them - is inflated
+        on the device too (:func:`_upload_gzip_device`: block and member starts found by probing, chunks of
+        ``gzip_chunk_bytes`` compressed bytes decoded against windows that are resolved afterwards); ``inflate`` is then
+        'device_gzip'.  Whatever the device does not take or finds damaged - an odd header, more member candidates than
+        its list holds, DEFLATE data, ISIZE or a CRC-32 that is wrong, memory that runs out - is read on the host exactly as
+        without the flag, errors included; ``inflate`` is 'host' then and ``inflate_stats['status']`` names the device's
+        reason.  ``inflate_stats``: chunks, candidates (chunks in which a block start was found), live (segments that were
+        decoded side by side), text_bytes, members, member_candidates (offsets that read like a member's start), status
+        (None: the device's gzip path was not tried), and bad_member / bad_member_offset where the device names one.  ``gzip_chunk_bytes``: a multiple of 16 in 256..2^24 (GZIP_CHUNK_BYTES)."""
         chunk = int(GZIP_CHUNK_BYTES if gzip_chunk_bytes is None else gzip_chunk_bytes)
         if chunk < 256 or chunk > (1 << 24) or chunk % 16:
             raise ValueError('gzip_chunk_bytes must be a multiple of 16 in 256..2^24')
@@ -584,9 +585,12 @@ def _upload_bgzf_file(torch, dev, path, n_blocks, total, blocks_per_launch=None)
 
 GZIP_CHUNK_BYTES = 65536                 # compressed bytes per chunk of the device's gzip inflate
 GZIP_INFO_WORDS = 8                      # include/besst_amd.h: BESST_GZIP_INFO_*
+GZIP_MEMBER_INFO_WORDS = 16              # BESST_GZIP_MEMBER_INFO_WORDS: the words above, then ...
+GZIP_INFO_MEMBERS, GZIP_INFO_BAD_MEMBER = 8, 10          # ... _MEMBERS, _MEMBER_CANDIDATES, _BAD_MEMBER, _BAD_MEMBER_OFFSET
+GZIP_MEMBER_CAPACITY = None              # member candidates the device's list holds (None: gzip_member_capacity's rule)
 GZIP_HEADER_ROOM = 1 << 17               # bytes of the file in which the member's header must end
 GZIP_STATUS = ('ok', 'block_type', 'stored_length', 'code_lengths', 'oversubscribed_code', 'bad_code', 'bad_distance',
-               'output_overrun', 'input_overrun', 'isize', 'crc', 'trailing_bytes')
+               'output_overrun', 'input_overrun', 'isize', 'crc', 'trailing_bytes', 'too_many_members')
 GZIP_STEPS = (('probe', 'count', 'link'), ('decode', 'windows', 'translate', 'crc'))
 GZIP_KERNEL_TIMES = None                 # a dict here (tools/time_fasta_ingest.py) is filled with the steps' milliseconds
 
@@ -628,12 +632,23 @@ def _gzip_steps(torch, names, call):
         times[name] = t0.elapsed_time(t1)
 
 
+def gzip_member_capacity(comp_bytes):
+    """The member candidates the device's list holds for a file of ``comp_bytes``: GZIP_MEMBER_CAPACITY where it is set,
+    else a candidate per 256 bytes of the file and 4096 more (the workspace is sized from the file's geometry alone; a
+    file of smaller members than that throughout is the host's: status 'too_many_members')."""
+    if GZIP_MEMBER_CAPACITY is not None:
+        return int(GZIP_MEMBER_CAPACITY)
+    return int(comp_bytes) // 256 + 4096
+
+
 def _upload_gzip_device(torch, dev, path, chunk_bytes, stats):
-    """A file that is ONE gzip member, inflated on the device (csrc/gzip_stream.hip): the compressed file goes up as it is
-    (_upload_file); besst_dev_gzip_plan finds the chunks that can be decoded side by side and the text's size - the one
-    read from the device in the middle -, besst_dev_gzip_inflate decodes, resolves the windows and checks the CRC-32.
-    -> (text, n) as _upload_file, or None with stats['status'] saying why: the caller reads the file on the host, which
-    also words the error where the file is damaged.  Every temporary is let go before that."""
+    """A file that is a series of gzip members, inflated on the device (csrc/gzip_stream.hip): the compressed file goes up
+    as it is (_upload_file); besst_dev_gzip_members_plan finds the chunks and the members that can be decoded side by side
+    and the text's size - the one read from the device in the middle -, besst_dev_gzip_members_inflate decodes, resolves
+    the windows and checks every member's CRC-32.
+    -> (text, n) as _upload_file, or None with stats['status'] saying why (and, where the device names one,
+    stats['bad_member'] and stats['bad_member_offset']): the caller reads the file on the host, which also words the error
+    where the file is damaged.  Every temporary is let go before that."""
     lib = _lib.load()
     p = _C.c_void_p
     size = os.path.getsize(path)
@@ -642,34 +657,46 @@ def _upload_gzip_device(torch, dev, path, chunk_bytes, stats):
     if data_off is None or size < data_off + 8:
         stats['status'] = 'header'
         return None
-    plan_bytes = lib.besst_dev_gzip_plan_workspace_bytes(size, data_off, chunk_bytes)
+    cap = gzip_member_capacity(size)
+    plan_bytes = lib.besst_dev_gzip_members_plan_workspace_bytes(size, data_off, chunk_bytes, cap)
     if not plan_bytes:
         stats['status'] = 'file_size'
         return None
     stream = p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def bad_member(words):
+        if words[GZIP_INFO_BAD_MEMBER] >= 0:                     # (-1: the device names none)
+            stats.update(bad_member=words[GZIP_INFO_BAD_MEMBER], bad_member_offset=words[GZIP_INFO_BAD_MEMBER + 1])
     try:
         comp, _ = _upload_file(torch, dev, path)
         plan = torch.empty(plan_bytes, dtype=torch.uint8, device=dev)
-        info = torch.zeros(GZIP_INFO_WORDS, dtype=torch.int64, device=dev)
-        _gzip_steps(torch, GZIP_STEPS[0], lambda steps: _lib.check(lib.besst_dev_gzip_plan(
-            stream, p(comp.data_ptr()), size, data_off, chunk_bytes, steps, p(plan.data_ptr()), plan_bytes, p(info.data_ptr())),
-            'besst_dev_gzip_plan'))
-        status, n, chunks, candidates, live = info.cpu().tolist()[:5]     # the one read in the middle: the text's size
-        stats.update(chunks=chunks, candidates=candidates, live=live, text_bytes=n, status=GZIP_STATUS[status])
+        info = torch.zeros(GZIP_MEMBER_INFO_WORDS, dtype=torch.int64, device=dev)
+        _gzip_steps(torch, GZIP_STEPS[0], lambda steps: _lib.check(lib.besst_dev_gzip_members_plan(
+            stream, p(comp.data_ptr()), size, data_off, chunk_bytes, cap, steps, p(plan.data_ptr()), plan_bytes,
+            p(info.data_ptr())), 'besst_dev_gzip_members_plan'))
+        words = info.cpu().tolist()                              # the one read in the middle: the text's size
+        status, n, chunks, candidates, live = words[:5]
+        members, member_candidates = words[GZIP_INFO_MEMBERS:GZIP_INFO_MEMBERS + 2]
+        stats.update(chunks=chunks, candidates=candidates, live=live, text_bytes=n, status=GZIP_STATUS[status], members=members,
+                     member_candidates=member_candidates)
         if status:
+            bad_member(words)
             return None
-        ws_bytes = lib.besst_dev_gzip_inflate_workspace_bytes(n, live)
+        ws_bytes = lib.besst_dev_gzip_members_inflate_workspace_bytes(n, live, members)
         if not ws_bytes:
             stats['status'] = 'file_size'
             return None
         text = torch.empty(n + EMIT_PAD, dtype=torch.uint8, device=dev)
         text[n:].zero_()
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _gzip_steps(torch, GZIP_STEPS[1], lambda steps: _lib.check(lib.besst_dev_gzip_inflate(
-            stream, p(comp.data_ptr()), size, data_off, chunk_bytes, steps, p(plan.data_ptr()), live, n, p(text.data_ptr()),
-            p(ws.data_ptr()), ws_bytes, p(info.data_ptr())), 'besst_dev_gzip_inflate'))
-        status = int(info[0].item())
+        _gzip_steps(torch, GZIP_STEPS[1], lambda steps: _lib.check(lib.besst_dev_gzip_members_inflate(
+            stream, p(comp.data_ptr()), size, data_off, chunk_bytes, cap, steps, p(plan.data_ptr()), live, members, n,
+            p(text.data_ptr()), p(ws.data_ptr()), ws_bytes, p(info.data_ptr())), 'besst_dev_gzip_members_inflate'))
+        words = info.cpu().tolist()
+        status = words[0]
         stats.update(status=GZIP_STATUS[status], plan_bytes=int(plan_bytes), workspace_bytes=int(ws_bytes))
+        if status:
+            bad_member(words)
         return (text, n) if not status else None
     except torch.cuda.OutOfMemoryError:
         stats['status'] = 'allocation'

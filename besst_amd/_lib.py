@@ -264,6 +264,11 @@ _SIGNATURES = {
     'besst_dev_gzip_inflate_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
     'besst_dev_gzip_inflate': (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P,
                                          C.c_size_t, _P]),
+    'besst_dev_gzip_members_plan_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    'besst_dev_gzip_members_plan': (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, C.c_size_t, _P]),
+    'besst_dev_gzip_members_inflate_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    'besst_dev_gzip_members_inflate': (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64,
+                                                 C.c_int64, C.c_int64, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -8,8 +8,8 @@ Flag names and defaults follow runBESST:254-402 for everything the hot path read
 goes on like runBESST's loop without path extension: the graph is linearised, the paths become scaffolds, and every pass
 writes ``pass<n>/Scaffolds-pass<n>.fa`` with its ``.agp`` and ``.gff`` (the sequence work on the GPU).  With
 ``--fasta_on_gpu`` the contig FASTA is parsed on the GPU into the sequence store instead of line by line in Python; a BGZF file is
-inflated there as well, and with ``--gzip_on_gpu`` so is a plain ``gzip`` file (one member; anything else is read by zlib on
-the host, as without the flag).  With
+inflated there as well, and with ``--gzip_on_gpu`` so is any other ``gzip`` file, of one member or of several (what the
+device gives up on is read by zlib on the host, as without the flag).  With
 ``--outputs_on_gpu`` the AGP and GFF text is formatted on the GPU too, and ``repeats.fa`` / ``low_coverage_contigs.fa`` are
 written from the sequence store in one go where the contigs live there (``--fasta_on_gpu``).  ``--final_fasta`` leaves the
 directory as runBESST does without --separate_repeats: ``pass<n>/Scaffolds_pass<n>.fa`` holds the scaffolds followed by
@@ -96,7 +96,8 @@ def build_parser():
                          'Python strings.  A BGZF file (bgzip, --bgzf_outputs) is inflated on the GPU too; any other gzip '
                          'file by zlib on the host')
     ap.add_argument('--gzip_on_gpu', dest='gzip_on_gpu', action='store_true',
-                    help="with --fasta_on_gpu: a contig FASTA that is plain gzip (gzip's own output, one member) is inflated on "
+                    help="with --fasta_on_gpu: a contig FASTA that is gzip but not BGZF (gzip's own output; one member or "
+                         'several, as cat, gzip -c >> and multi-member compressors leave them) is inflated on '
                          'the GPU as well - block starts found by probing, chunks decoded side by side, CRC-32 checked; what '
                          'the GPU does not take is read by zlib on the host as without the flag; needs --fasta_on_gpu')
     ap.add_argument('--outputs_on_gpu', dest='outputs_on_gpu', action='store_true',

@@ -6,6 +6,9 @@
 //   walk_chunk             block after block from a start bit to the landing: lengths only (the count), or 16-bit symbols
 //                          (the decode): a literal, or kMarker | k = "byte k of the 32 KiB in front of this chunk"
 //   link_chain             the live chunks: the landings followed from chunk 0, their places in the text
+//   member_magic / member_data_offset / member_find / link_members   a file of SEVERAL members: the byte offsets that read
+//                          like a member's start, a header's end, the list of those offsets, and the chain that passes
+//                          from a member's final block over its trailer to the next member's first block
 //   resolve_symbol         a 16-bit symbol -> its byte, given the text in front of the chunk
 // Bit positions count from the first byte of the FILE (bit 0 of byte 0 is position 0), LSB first as RFC 1951 packs them.
 // Everything a wave does in step is written for `lane` of `nlanes`: the device runs 64 lanes, the host one (or 64, one
@@ -26,7 +29,7 @@ namespace gz {
 // status of a chunk, and of the member (0 = good).  9 and 10 are BGZF's BESST_BGZF_BAD_SIZE / BESST_BGZF_BAD_CRC.
 enum : uint32_t {
     kOk = 0, kBadBlockType, kBadStored, kBadLengths, kOversubscribed, kBadCode, kBadDistance, kOutputOverrun, kInputOverrun,
-    kBadSize, kBadCrc, kTrailingBytes, kStatusCount
+    kBadSize, kBadCrc, kTrailingBytes, kTooManyMembers, kStatusCount
 };
 
 constexpr uint32_t kNoCandidate = 0xffffffffu;
@@ -282,8 +285,9 @@ struct WalkArgs {
     // the count: a block end that is the candidate of the chunk it lies in is the landing
     const uint32_t* cand_rel;        // per chunk: its candidate's bit, counted from the chunk's first (kNoCandidate: none)
     uint64_t n_chunks, data_bit0, chunk_bits;
-    // the decode: the landing found by the count, the bytes until there, the chunk's place in the text
-    uint64_t stop_bit, out_cap, text_off;
+    // the decode: the landing found by the count, the bytes until there, the chunk's place in the text, and the place
+    // where its member's text begins (a match may reach that byte and not one further)
+    uint64_t stop_bit, out_cap, text_off, member_off;
 };
 struct WalkResult {
     uint64_t land_bit, out_bytes;
@@ -377,7 +381,7 @@ GZ_FN WalkResult walk_chunk(Ctx& c, WalkTables& t, const WalkArgs& a) {
                 c.drop((e & 15u) + (dc >> 16));
                 if (kWrite) {
                     if (pos + len > a.out_cap) { st = kOutputOverrun; break; }
-                    if (dist > pos + a.text_off) { st = kBadDistance; break; }     // in front of the text's first byte
+                    if (dist > pos + (a.text_off - a.member_off)) { st = kBadDistance; break; }   // in front of the member's first byte
                     // byte i of the match is byte i mod dist of the dist bytes in front of it: every source lies in front of
                     // the match, inside the chunk (its symbol is copied) or in the window (a marker)
                     for (uint32_t i = c.lane; i < len; i += c.nlanes) {
@@ -432,6 +436,157 @@ GZ_FN uint32_t link_chain(const uint64_t* land, const uint64_t* out_bytes, const
     *text_bytes = off;
     *n_live = n;
     return st;
+}
+
+// ---- a file of several members ---------------------------------------------------------------------------------------------
+// A member start is FOUND like a block start: every byte offset behind the first that reads 1f 8b 08 and a FLG without
+// reserved bits is a member candidate, whatever it lies in (compressed data, a stored block, another header's FNAME).  The
+// candidates are kept as a list (in the order their finders arrived) with a chain per kMemberBucketBytes of the file, so
+// that the link finds the one at a given offset; each has its header parsed and its first blocks walked by a wave of its own.
+// The chain from member 0 then asks only for the candidate behind a trailer: every other one is dropped unseen.
+constexpr uint64_t kNoMember = ~(uint64_t)0;
+constexpr uint32_t kHeaderFieldLimit = 65536u;    // bytes a header's FNAME or FCOMMENT may take, its zero included
+constexpr uint32_t kMemberBucketBytes = 4096u;
+constexpr uint32_t kCrcSliceBytes = 1024u, kCrcGroupSlices = 64u;
+
+GZ_FN bool member_magic(uint32_t w) {                        // the four bytes at an offset, little endian: ID1 ID2 CM FLG
+    return (w & 0xffffffu) == 0x088b1fu && ((w >> 24) & 0xe0u) == 0u;
+}
+
+// The member header at byte `at` -> the offset of its DEFLATE data (the device's twin of GenerateOutput.gzip_header_bytes:
+// CM = 8, no reserved flag, FEXTRA / FNAME / FCOMMENT / FHCRC skipped), kNoMember: not a header, a field that does not
+// end inside the file or inside kHeaderFieldLimit, or no room for two bits of data and a trailer behind it.
+GZ_FN uint64_t member_data_offset(const uint8_t* data, uint64_t n_bytes, uint64_t at) {
+    if (at > n_bytes || n_bytes - at < 18u) return kNoMember;
+    if (data[at] != 0x1fu || data[at + 1u] != 0x8bu || data[at + 2u] != 8u || (data[at + 3u] & 0xe0u)) return kNoMember;
+    const uint32_t flg = data[at + 3u];
+    uint64_t p = at + 10u;
+    if (flg & 4u) {
+        if (n_bytes - p < 2u) return kNoMember;
+        p += 2u + ((uint32_t)data[p] | ((uint32_t)data[p + 1u] << 8));
+    }
+    for (uint32_t bit = 8u; bit <= 16u; bit <<= 1) {
+        if (!(flg & bit)) continue;
+        for (uint32_t k = 0;; ++k) {
+            if (p >= n_bytes || k >= kHeaderFieldLimit) return kNoMember;
+            if (data[p++] == 0u) break;
+        }
+    }
+    if (flg & 2u) p += 2u;
+    return p <= n_bytes && n_bytes - p >= 8u ? p : kNoMember;
+}
+
+// the member candidates: off[i] the offset, next[i] the chain of its bucket, head[b] the chain's first (kNoCandidate: none)
+struct MemberList {
+    const uint64_t* off;
+    const uint32_t *next, *head;
+    uint64_t n_buckets;
+    uint32_t n;                      // candidates in the list
+};
+GZ_FN uint32_t member_find(const MemberList& l, uint64_t at) {
+    const uint64_t b = at / kMemberBucketBytes;
+    if (b >= l.n_buckets) return kNoCandidate;
+    uint32_t i = l.head[b];
+    for (uint32_t turns = 0; turns < l.n && i < l.n; ++turns) {
+        if (l.off[i] == at) return i;
+        i = l.next[i];
+    }
+    return kNoCandidate;
+}
+
+// a live member: where it lies in the file and in the text, and where its CRC slices and groups begin (the 1 KiB grid
+// restarts at every member's first byte)
+struct MemberRow {
+    uint64_t comp_off, trailer_off, text_off, text_bytes, slice0, group0;
+};
+GZ_FN uint64_t crc_slices_of(uint64_t bytes) { return (bytes + kCrcSliceBytes - 1u) / kCrcSliceBytes; }
+GZ_FN uint64_t crc_groups_of(uint64_t bytes) { return (crc_slices_of(bytes) + kCrcGroupSlices - 1u) / kCrcGroupSlices; }
+// the member that holds slice (kGroup: group) `s`: the last row that begins at or in front of it (members without text
+// share their successor's first slice and are passed over)
+template <bool kGroup>
+GZ_FN uint64_t member_of(const MemberRow* rows, uint64_t n_members, uint64_t s) {
+    uint64_t lo = 0, hi = n_members;                         // rows[lo] begins <= s < rows[hi] begins
+    while (hi - lo > 1u) {
+        const uint64_t mid = lo + (hi - lo) / 2u;
+        if ((kGroup ? rows[mid].group0 : rows[mid].slice0) <= s) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// The walks: [0, n_chunks) from the chunks' candidates, n_chunks + i from member candidate i's data (m_start[i]: its first
+// bit, kNoMember: no header).  Segments, not chunks, are live: several may begin in one chunk.
+struct LinkArgs {
+    const uint8_t* data;             // the file
+    uint64_t n_bytes;
+    const uint32_t* cand_rel;
+    uint64_t n_chunks, data_bit0, chunk_bits;
+    const uint64_t *land, *out_bytes;            // per walk
+    const uint32_t *final_block, *status;
+    const uint64_t* m_start;
+    MemberList members;
+    uint64_t seg_cap, row_cap;       // room in live_* and in rows
+};
+struct LinkResult {
+    uint64_t text_bytes, n_live, n_members, end_bit, bad_member, bad_member_offset;
+    uint32_t status;
+};
+GZ_FN uint32_t link_le32(const uint8_t* p) {
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+// Follows the landings from member 0's data: live_idx the walks on the chain, live_off their places in the text, live_mem
+// the place where each one's member begins; rows the members.  At a final block: ISIZE against the member's bytes, then
+// the file's end, or the candidate behind the trailer.  The status is that of the first walk or member that has one.
+GZ_FN LinkResult link_members(const LinkArgs& a, uint32_t* live_idx, uint64_t* live_off, uint64_t* live_mem, MemberRow* rows) {
+    LinkResult r = {0, 0, 0, 0, kNoMember, 0, kOk};
+    // w: the walk; cur: the member it belongs to, which begins at byte mem_at of the file and mem_off of the text
+    uint64_t w = 0, n = 0, off = 0, cur = 0, rows_made = 0, mem_off = 0, mem_at = 0, slice0 = 0, group0 = 0;
+    uint64_t start = a.data_bit0;
+    for (;;) {
+        if (n >= a.seg_cap || cur >= a.row_cap) { r.status = kInputOverrun; break; }   // (every turn begins behind the one before)
+        live_idx[n] = (uint32_t)w;
+        live_off[n] = off;
+        live_mem[n] = mem_off;
+        ++n;
+        if (a.status[w]) { r.status = a.status[w]; break; }
+        const uint64_t land = a.land[w];
+        if (land <= start) { r.status = kInputOverrun; break; }
+        off += a.out_bytes[w];
+        r.end_bit = land;
+        if (!a.final_block[w]) {
+            const uint64_t j = (land - a.data_bit0) / a.chunk_bits;
+            if (j >= a.n_chunks || a.cand_rel[j] == kNoCandidate || a.data_bit0 + j * a.chunk_bits + a.cand_rel[j] != land) {
+                r.status = kInputOverrun;
+                break;
+            }
+            w = j;
+            start = land;
+            continue;
+        }
+        const uint64_t trailer = (land + 7u) >> 3, bytes = off - mem_off;       // (the walk ends in front of the last 8 bytes)
+        if (trailer + 8u > a.n_bytes) { r.status = kInputOverrun; break; }
+        const MemberRow row = {mem_at, trailer, mem_off, bytes, slice0, group0};
+        rows[cur] = row;
+        rows_made = cur + 1u;
+        slice0 += crc_slices_of(bytes);
+        group0 += crc_groups_of(bytes);
+        if (link_le32(a.data + trailer + 4u) != (uint32_t)bytes) { r.status = kBadSize; break; }
+        if (trailer + 8u == a.n_bytes) break;
+        ++cur;
+        mem_at = trailer + 8u;
+        mem_off = off;
+        const uint32_t i = member_find(a.members, mem_at);
+        if (i == kNoCandidate || a.m_start[i] == kNoMember) { r.status = kTrailingBytes; break; }   // the host words it
+        w = a.n_chunks + i;
+        start = a.m_start[i];
+    }
+    r.text_bytes = off;
+    r.n_live = n;
+    r.n_members = rows_made;
+    if (r.status) {
+        r.bad_member = cur;
+        r.bad_member_offset = mem_at;
+    }
+    return r;
 }
 
 // ---- a symbol's byte: `front` points at the first byte of the symbol's chunk in the text ----------------------------------

@@ -43,7 +43,9 @@ extern "C" {
  * besst_dev_bgzf_deflate_bound / besst_dev_bgzf_deflate_workspace_bytes / besst_dev_bgzf_deflate / besst_bgzf_deflate_device;
  * the inflate of a BGZF file in device memory besst_bgzf_walk / besst_bgzf_scan_chunk /
  * besst_dev_bgzf_inflate_workspace_bytes / besst_dev_bgzf_inflate; of a plain gzip member besst_dev_gzip_plan_workspace_bytes /
- * besst_dev_gzip_plan / besst_dev_gzip_inflate_workspace_bytes / besst_dev_gzip_inflate; the run bits of the record layout besst_dev_record_bits
+ * besst_dev_gzip_plan / besst_dev_gzip_inflate_workspace_bytes / besst_dev_gzip_inflate, of a gzip file of several members
+ * besst_dev_gzip_members_plan_workspace_bytes / besst_dev_gzip_members_plan / besst_dev_gzip_members_inflate_workspace_bytes /
+ * besst_dev_gzip_members_inflate; the run bits of the record layout besst_dev_record_bits
  * with the trailing member besst_lib_params.tid_bits (see there); the candidate side stream besst_cand_stream with
  * besst_dev_candidate_offsets_bytes / besst_dev_candidate_stream_bytes / besst_dev_candidate_offsets /
  * besst_dev_candidate_stream, the trailing member besst_lib_params.cand_stream, and besst_dev_record_loop_form; the layout
@@ -405,6 +407,39 @@ size_t besst_dev_gzip_inflate_workspace_bytes(int64_t text_bytes, int64_t n_live
 int besst_dev_gzip_inflate(void* stream, const void* comp, int64_t comp_bytes, int64_t data_off, int64_t chunk_bytes,
                            int32_t steps, const void* plan_workspace, int64_t n_live, int64_t text_bytes, void* text,
                            void* workspace, size_t workspace_bytes, uint64_t* info);
+
+/* ---- a gzip file of SEVERAL members (RFC 1952: `cat a.gz b.gz`, multi-member compressors, `gzip -c >>`, a BGZF chain behind
+ * or in front of a foreign member), inflated the same way into one text.  The four calls above, member-aware; the file's
+ * first member begins at byte 0 and its DEFLATE data at data_off, every later member is found on the device:
+ *   - every byte offset behind the first that reads 1f 8b 08 and a FLG without reserved bits is a MEMBER CANDIDATE; the
+ *     list holds member_cap of them (0..2^28; GenerateOutput.py asks for comp_bytes / 256 + 4096).  More than that:
+ *     BESST_GZIP_TOO_MANY_MEMBERS, and nothing else is looked at.  A candidate's header is parsed on the device (CM = 8;
+ *     FEXTRA, FNAME, FCOMMENT - 65536 bytes each at most - and FHCRC skipped), and its first blocks are walked by a wave
+ *     of its own.  Candidates that are no member (in compressed data, a stored block, another header) are never asked for.
+ *   - the link passes from a member's final block over its trailer (ISIZE against the member's own bytes) to the candidate
+ *     that begins at the next byte; none there, or no header: BESST_GZIP_TRAILING.  What is live is a SEGMENT (the walk
+ *     from a chunk's candidate or from a member's first block): n_live may exceed the number of chunks.
+ *   - a match may reach its member's first byte and not one further (BESST status 6), and every member's CRC-32 is held
+ *     against its own trailer; the first bad member by file order is the one reported.
+ * info[0..16) (device): the words above (_CRC: the last member's), then _MEMBERS (members on the chain), _MEMBER_CANDIDATES
+ * (as counted, also when they are too many), _BAD_MEMBER (index by file order of the member the status is about, ~0: none)
+ * and _BAD_MEMBER_OFFSET (its first byte in the file); the rest is 0.  Still one read of info between plan and inflate:
+ * n_live, n_members and text_bytes come from it.  On a file of one member chunks, candidates, live and text are what
+ * besst_dev_gzip_plan leaves. */
+#define BESST_GZIP_TOO_MANY_MEMBERS 12
+#define BESST_GZIP_MEMBER_INFO_WORDS 16
+#define BESST_GZIP_INFO_MEMBERS 8
+#define BESST_GZIP_INFO_MEMBER_CANDIDATES 9
+#define BESST_GZIP_INFO_BAD_MEMBER 10
+#define BESST_GZIP_INFO_BAD_MEMBER_OFFSET 11
+size_t besst_dev_gzip_members_plan_workspace_bytes(int64_t comp_bytes, int64_t data_off, int64_t chunk_bytes, int64_t member_cap);
+int besst_dev_gzip_members_plan(void* stream, const void* comp, int64_t comp_bytes, int64_t data_off, int64_t chunk_bytes,
+                                int64_t member_cap, int32_t steps, void* workspace, size_t workspace_bytes, uint64_t* info);
+size_t besst_dev_gzip_members_inflate_workspace_bytes(int64_t text_bytes, int64_t n_live, int64_t n_members);
+int besst_dev_gzip_members_inflate(void* stream, const void* comp, int64_t comp_bytes, int64_t data_off, int64_t chunk_bytes,
+                                   int64_t member_cap, int32_t steps, const void* plan_workspace, int64_t n_live,
+                                   int64_t n_members, int64_t text_bytes, void* text, void* workspace, size_t workspace_bytes,
+                                   uint64_t* info);
 
 /* libmetrics sampling (replaces the three `for read in bam_file` scans, libmetrics.py:63,257,293).
  * top_mask[tid] != 0 marks the 1000 longest references.  orientation/min_mapq/read_len as in

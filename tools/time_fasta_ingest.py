@@ -12,7 +12,9 @@
     at levels 1 and 6 as one plain gzip member each (from_fasta inflates them on the host, and with gzip_on_gpu=True on the
     device: csrc/gzip_stream.hip) - wall time of from_fasta on every file and path, alternating in the same rounds,
     --gz_reps rounds, median and range, with the bytes each form sends over PCIe; the device gzip path's kernels one by
-    one (a run of their own) and its workspace; and cli.read_fasta on the BGZF file.
+    one (a run of their own) and its workspace; and cli.read_fasta on the BGZF file;
+  * the same text as SEVERAL gzip members at level 6 - 16 concatenated members, and members of 1 MiB of text each (about
+    1100) - on the host and on the device, in the same rounds.
 
     python tools/time_fasta_ingest.py --out profiles/fasta_ingest.json
 """
@@ -24,6 +26,7 @@ import sys
 import tempfile
 import time
 import zlib
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -65,11 +68,22 @@ def host_path(path):
 
 
 def write_compressed(path, work):
-    """-> {'bgzf': path, 'gzip': path (level 1), 'gzip6': path} of the FASTA at ``path``"""
+    """-> {'bgzf': path, 'gzip': path (level 1), 'gzip6': path, 'gzip6_m16': path (16 members), 'gzip6_1m': path (a member
+    per MiB of text)} of the FASTA at ``path``"""
     with open(path, 'rb') as fh:
         raw = fh.read()
     out = dict(bgzf=os.path.join(work, 'contigs.bgzf.fa.gz'), gzip=os.path.join(work, 'contigs.gzip.fa.gz'),
-               gzip6=os.path.join(work, 'contigs.gzip6.fa.gz'))
+               gzip6=os.path.join(work, 'contigs.gzip6.fa.gz'), gzip6_m16=os.path.join(work, 'contigs.gzip6_m16.fa.gz'),
+               gzip6_1m=os.path.join(work, 'contigs.gzip6_1m.fa.gz'))
+
+    def member(piece):
+        comp = zlib.compressobj(6, zlib.DEFLATED, 31)
+        return comp.compress(piece) + comp.flush()
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:         # (zlib lets go of the interpreter lock)
+        for kind, size in (('gzip6_m16', -(-len(raw) // 16)), ('gzip6_1m', 1 << 20)):
+            with open(out[kind], 'wb') as fh:
+                for part in pool.map(member, (raw[at:at + size] for at in range(0, len(raw), size))):
+                    fh.write(part)
     with open(out['bgzf'], 'wb') as fh:
         fh.write(GO.bgzf_compress(raw))
     for kind, level in (('gzip', 1), ('gzip6', 6)):
@@ -83,7 +97,10 @@ def write_compressed(path, work):
 
 # what is timed: (name in the report, file, from_fasta's keywords)
 RUNS = (('plain', 'plain', {}), ('bgzf', 'bgzf', {}), ('gzip', 'gzip', {}), ('gzip_device', 'gzip', {'gzip_on_gpu': True}),
-        ('gzip6', 'gzip6', {}), ('gzip6_device', 'gzip6', {'gzip_on_gpu': True}))
+        ('gzip6', 'gzip6', {}), ('gzip6_device', 'gzip6', {'gzip_on_gpu': True}),
+        ('gzip6_m16', 'gzip6_m16', {}), ('gzip6_m16_device', 'gzip6_m16', {'gzip_on_gpu': True}),
+        ('gzip6_1m', 'gzip6_1m', {}), ('gzip6_1m_device', 'gzip6_1m', {'gzip_on_gpu': True}))
+COMPRESSED = ('bgzf', 'gzip', 'gzip6', 'gzip6_m16', 'gzip6_1m')
 
 
 def compressed_runs(path, n, asm, reps, work):
@@ -94,7 +111,9 @@ def compressed_runs(path, n, asm, reps, work):
         doc = dict(file_bytes={k: os.path.getsize(v) for k, v in files.items()}, bgzf_blocks=n_blocks,
                    # what crosses PCIe on the way in: the file (and 24 bytes of descriptor per block), or the inflated text
                    pcie_bytes=dict(plain=n, bgzf=os.path.getsize(files['bgzf']) + GO.BGZF_DESC_BYTES * n_blocks, gzip=n, gzip6=n,
-                                   gzip_device=os.path.getsize(files['gzip']), gzip6_device=os.path.getsize(files['gzip6'])),
+                                   gzip6_m16=n, gzip6_1m=n, gzip_device=os.path.getsize(files['gzip']),
+                                   gzip6_device=os.path.getsize(files['gzip6']), gzip6_m16_device=os.path.getsize(files['gzip6_m16']),
+                                   gzip6_1m_device=os.path.getsize(files['gzip6_1m'])),
                    from_fasta_s={name: [] for name, _, _ in RUNS}, inflate={}, gzip_device={})
         for k in files.values():
             with open(k, 'rb') as fh:                            # page cache warm
@@ -135,9 +154,17 @@ def compressed_runs(path, n, asm, reps, work):
         doc['reps'] = reps
         return doc
     finally:
-        for kind in ('bgzf', 'gzip', 'gzip6'):
+        for kind in COMPRESSED:
             if os.path.exists(files[kind]):
                 os.remove(files[kind])
+
+
+def write_report(doc, out):
+    report = json.dumps(doc, indent=1, sort_keys=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as fh:
+        fh.write(report + '\n')
+    print(report)
 
 
 def main():
@@ -146,6 +173,7 @@ def main():
     ap.add_argument('--contigs', type=int, default=100_000)
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--gz_reps', type=int, default=3, help='rounds of from_fasta over the plain, the BGZF and the gzip files')
+    ap.add_argument('--compressed_only', action='store_true', help='only the rounds over the compressed files')
     args = ap.parse_args()
     import torch
     asm = OU.seeded_assembly(args.contigs, 3000, 20000, 17)
@@ -158,6 +186,9 @@ def main():
         with open(path, 'rb') as fh:                             # page cache warm for everything below
             while fh.read(64 << 20):
                 pass
+        if args.compressed_only:
+            doc['compressed'] = compressed_runs(path, n, asm, args.gz_reps, work)
+            return write_report(doc, args.out)
         # wall times, both orders
         walls = []
         for order in (('device', 'host'), ('host', 'device')):
@@ -229,11 +260,7 @@ def main():
     finally:
         os.remove(path)
         os.rmdir(work)
-    report = json.dumps(doc, indent=1, sort_keys=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as fh:
-        fh.write(report + '\n')
-    print(report)
+    write_report(doc, args.out)
 
 
 if __name__ == '__main__':
