@@ -68,6 +68,12 @@ class IngestStats(C.Structure):      # include/besst_amd.h: besst_ingest_stats
                 ('blocks', C.c_int64), ('on_device', C.c_int32), ('starts_repaired', C.c_int32)]
 
 
+class ReportArgs(C.Structure):       # include/besst_amd.h: besst_report_args
+    _fields_ = [('tid', C.c_void_p), ('mtid', C.c_void_p), ('pos', C.c_void_p), ('mpos', C.c_void_p), ('tlen', C.c_void_p),
+                ('flag', C.c_void_p), ('mapq', C.c_void_p), ('qlen', C.c_void_p), ('tid_bits', C.c_void_p),
+                ('n_records', C.c_int64), ('n_refs', C.c_int64), ('isize_bins', C.c_int64), ('out_words', C.c_int64)]
+
+
 class MetricsCounts(C.Structure):
     _fields_ = [('n_isize', C.c_int64), ('n_contam', C.c_int64), ('counter_total', C.c_int64),
                 ('sample_counter', C.c_int64), ('records_scanned', C.c_int64)]
@@ -142,6 +148,9 @@ _SIGNATURES = {
                                            C.POINTER(MetricsCounts)]),
     'besst_ctx_stream_order': (C.c_int, [_P, C.POINTER(C.c_int64), _P, _P]),
     'besst_dev_stream_order': (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    'besst_dev_library_report_words': (C.c_int64, [C.c_int64, C.c_int64]),
+    'besst_dev_library_report': (C.c_int, [_P, C.POINTER(ReportArgs), _P]),
+    'besst_ctx_library_report': (C.c_int, [_P, C.c_int64, _P, C.c_int64]),
     'besst_ctx_value_histogram': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
     'besst_ctx_build_graph': (C.c_int, [_P]),
     'besst_ctx_edge_count': (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -84,6 +84,13 @@ class ResidentBam(object):
         there already (all three watermarks at ``len()``), and the first build launches no maker."""
         return self.ctx.layout_state()
 
+    def report(self, isize_bins=32768):
+        """The BAM report of the file (GraphContext.library_report, besst_amd.report) with the header's names and lengths.
+        Over a ``part`` it describes that slice."""
+        rep = self.ctx.library_report(isize_bins)
+        rep.references, rep.lengths = list(self.references), [int(x) for x in self.lengths]
+        return rep
+
     def close(self):
         self.ctx.close()
 
@@ -115,6 +122,28 @@ class ShardedBam(object):
 
     def __len__(self):
         return len(self.head)
+
+    def report(self, isize_bins=32768):
+        """The BAM report of the WHOLE file on every rank (collective): each rank runs besst_dev_library_report over its
+        slice, the words are summed over the group - the digest's xor word is gathered and xor-ed instead."""
+        import torch
+        import torch.distributed as dist
+        from . import distributed, report, sharded
+        words, err = None, None
+        try:
+            words = report.dev_report_tensor(self.engine.rec, len(self.references), isize_bins)
+            xor_word = int(words[report.DIGEST_XOR].item())
+            words[report.DIGEST_XOR] = 0
+        except Exception as e:
+            err = '%s: %s' % (type(e).__name__, e)
+        sharded._agree(self.group, self.world, err)          # (nobody enters the all-reduce without the others)
+        distributed._all_reduce(words, self.group)
+        xors = [None] * self.world
+        dist.all_gather_object(xors, xor_word, group=self.group)
+        host = words.cpu().numpy().view(np.uint64).copy()
+        for x in xors:
+            host[report.DIGEST_XOR] ^= np.uint64(x & 0xffffffffffffffff)
+        return report.LibraryReport(host, len(self.references), isize_bins, self.references, self.lengths)
 
     def close(self):
         if self.engine is not None:

@@ -17,7 +17,9 @@ the repeats, ``Scaffolds-pass<n>.fa`` and, after the last pass, ``repeats.fa`` a
 scaffold FASTA is compressed on the GPU and written as ``Scaffolds-pass<n>.fa.gz``, a BGZF file (what ``bgzip`` writes:
 ``samtools faidx`` and every gzip reader open it), and no ``.fa``; ``--final_fasta`` then leaves
 ``Scaffolds_pass<n>.fa.gz``, the repeats appended as further BGZF blocks.  AGP, GFF, ``repeats.fa``,
-``low_coverage_contigs.fa`` and the TSVs stay plain.  BESST's path
+``low_coverage_contigs.fa`` and the TSVs stay plain.  With ``--bam_report`` every pass also counts what its BAM holds, in
+one pass over the resident records on the GPU, and writes ``pass<n>/bam_report.tsv``, ``idxstats.tsv``, ``mapq_hist.tsv``,
+``qlen_hist.tsv`` and ``insert_sizes.tsv`` (besst_amd.report).  BESST's path
 search (PROWithinScaf / PROBetweenScaf) stays with BESST - see INTEGRATION.md for plugging these calls into runBESST.
 
 Several GPUs of one node: launch the same command line under torchrun, one process per GPU -
@@ -39,7 +41,7 @@ from time import time
 from . import CreateGraph as CG
 from . import GenerateOutput as GO
 from . import MakeScaffolds as MS
-from . import Parameter, bamio, libmetrics, mathstats_compat, session
+from . import Parameter, bamio, libmetrics, mathstats_compat, report, session
 
 
 def open_fasta(path):
@@ -113,6 +115,12 @@ def build_parser():
     ap.add_argument('-filter_contigs', dest='contig_filter_length', type=int, default=None,
                     help='leave contigs shorter than this out of the run (runBESST -filter_contigs)')
     ap.add_argument('--threads', type=int, default=None, help='BAM inflate threads')
+    ap.add_argument('--bam_report', dest='bam_report', action='store_true',
+                    help='per pass, count what the BAM holds in one pass over the resident records on the GPU and write '
+                         'pass<n>/bam_report.tsv (the rows of samtools flagstat, the pair classes, a digest of the columns), '
+                         'idxstats.tsv (the numbers of samtools idxstats), mapq_hist.tsv, qlen_hist.tsv and insert_sizes.tsv; '
+                         'the census goes to Statistics.txt too, with a note when the pairs speak against -orientation or '
+                         "the contig lengths against the header's")
     ap.add_argument('--linearize', action='store_true',
                     help="also run steps 1-4 of MakeScaffolds.Algorithm on a copy of G (isolated scaffolds, "
                          "score-based ambiguity removal, cycles) and write the surviving link edges")
@@ -158,6 +166,34 @@ def write_scaffolds(G, G_prime, Contigs, small_contigs, Scaffolds, small_scaffol
         F = GO.WriteToF(F, Contigs, Scaffolds[scaffold_].contigs)
     GO.PrintOutput(F, Information, param.output_directory, param, pass_nr, store=store)
     print('Time elapsed for writing the scaffolds, iteration ' + str(pass_nr - 1) + ': ' + str(time() - t0) + '\n',
+          file=Information)
+
+
+def write_bam_report(records, param, C_dict, pass_dir, Information, lead):
+    """--bam_report: the report of the opened BAM (every rank takes part under a process group; rank 0 writes) as files
+    in the pass's directory, the census in Statistics.txt, and the two notes - the pairs against the named orientation, the
+    FASTA's contig lengths against the header's.  The run goes on unchanged."""
+    t0 = time()
+    rep = records.report()
+    if not lead:
+        return
+    rep.write(pass_dir)
+    print('BAM report of %s (pass%d/bam_report.tsv, idxstats.tsv, mapq_hist.tsv, qlen_hist.tsv, insert_sizes.tsv):'
+          % (param.bamfile, param.pass_number), file=Information)
+    for line in rep.census_lines():
+        print(line, file=Information)
+    note = report.orientation_note(rep, param.orientation)
+    if note:
+        print(note, file=sys.stderr)
+        print(note, file=Information)
+    bad = report.length_mismatches(records.references, records.lengths, {name: len(seq) for name, seq in C_dict.items()})
+    if bad:
+        text = ('NOTE: %d contig(s) have another length in the contig file than in the header of %s (was it mapped to '
+                'another contig file?): %s' % (len(bad), param.bamfile,
+                                               ', '.join('%s (%d, header %d)' % (n, fl, hl) for n, hl, fl in bad[:10])))
+        print(text, file=sys.stderr)
+        print(text, file=Information)
+    print('Time elapsed for the BAM report, iteration ' + str(param.pass_number - 1) + ': ' + str(time() - t0) + '\n',
           file=Information)
 
 
@@ -301,6 +337,8 @@ def _run(args, rank):
         records = bamio.open_bam(bam, threads=args.threads)
         print('Time elapsed reading %s (%d records): %s' % (bam, len(records), time() - t0), file=Information)
         param.contig_index = dict(enumerate(records.references))
+        if args.bam_report:
+            write_bam_report(records, param, C_dict, os.path.join(out, 'pass%d' % (i + 1)), Information, lead)
         t0 = time()
         libmetrics.get_metrics(records, param, Information)
         print('Time elapsed for getting libmetrics, iteration ' + str(i) + ': ' + str(time() - t0) + '\n',

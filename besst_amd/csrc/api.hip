@@ -1136,6 +1136,49 @@ int besst_ctx_stream_order(besst_ctx* c, int64_t* first_unsorted, int32_t* first
     return BESST_OK;
 }
 
+int64_t besst_dev_library_report_words(int64_t n_refs, int64_t isize_bins) {
+    if (n_refs < 0 || n_refs >= ((int64_t)1 << 31) || isize_bins < 1 || isize_bins > BESST_REPORT_MAX_ISIZE_BINS) return 0;
+    return (int64_t)BESST_REPORT_REFS + 2 * n_refs + 3 * (isize_bins + 1);
+}
+
+int besst_dev_library_report(void* stream, const besst_report_args* a, uint64_t* out) {
+    BESST_REQUIRE(a && out, "dev_library_report: null pointer");
+    BESST_REQUIRE(a->n_records >= 0 && a->n_records < ((int64_t)1 << 32), "dev_library_report: n_records out of range");
+    BESST_REQUIRE(a->n_refs >= 0 && a->n_refs < ((int64_t)1 << 31), "dev_library_report: n_refs out of range");
+    BESST_REQUIRE(a->isize_bins >= 1 && a->isize_bins <= BESST_REPORT_MAX_ISIZE_BINS,
+                  "dev_library_report: isize_bins must lie in 1 .. 2^20");
+    const int64_t words = besst_dev_library_report_words(a->n_refs, a->isize_bins);
+    BESST_REQUIRE(a->out_words >= words, "dev_library_report: the result buffer is too short");
+    BESST_REQUIRE(a->n_records == 0 || (a->tid && a->mtid && a->pos && a->mpos && a->tlen && a->flag && a->mapq && a->qlen),
+                  "dev_library_report: null column");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    BESST_HIP_TRY(hipMemsetAsync(out, 0, (size_t)words * 8, s));
+    return launch_library_report(s, *a, reinterpret_cast<unsigned long long*>(out));
+}
+
+int besst_ctx_library_report(besst_ctx* c, int64_t isize_bins, uint64_t* out_host, int64_t out_words) {
+    BESST_REQUIRE(c && out_host, "library_report: null pointer");
+    BESST_REQUIRE(isize_bins >= 1 && isize_bins <= BESST_REPORT_MAX_ISIZE_BINS, "library_report: isize_bins must lie in 1 .. 2^20");
+    const int64_t words = besst_dev_library_report_words(c->n_contigs, isize_bins);
+    BESST_REQUIRE(words > 0 && out_words >= words, "library_report: the result buffer is too short");
+    int rc = use_device(c);
+    if (rc) return rc;
+    if ((rc = c->aux.ensure((size_t)words * 8))) return rc;
+    besst_report_args a{};
+    a.tid = c->tid.p; a.mtid = c->mtid.p; a.pos = c->pos.p; a.mpos = c->mpos.p; a.tlen = c->tlen.p;
+    a.flag = c->flag.p; a.mapq = c->mapq.p; a.qlen = c->qlen.p;
+    a.tid_bits = nullptr;
+    a.n_records = c->n_records;
+    a.n_refs = c->n_contigs;
+    a.isize_bins = isize_bins;
+    a.out_words = words;
+    uint64_t* d_out = reinterpret_cast<uint64_t*>(c->aux.p);
+    if ((rc = besst_dev_library_report(c->stream, &a, d_out))) return rc;
+    BESST_HIP_TRY(hipMemcpyAsync(out_host, d_out, (size_t)words * 8, hipMemcpyDeviceToHost, c->stream));
+    BESST_HIP_TRY(hipStreamSynchronize(c->stream));
+    return BESST_OK;
+}
+
 int besst_ctx_metrics_sample(besst_ctx* c, const uint8_t* top_mask, int32_t orientation, int32_t min_mapq,
                              double read_len, int32_t want_isize, int32_t* isize_out, int32_t* contam_out,
                              besst_metrics_counts* counts) {

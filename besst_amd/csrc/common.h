@@ -470,6 +470,8 @@ int launch_metrics(hipStream_t s, const MetricsArgs& a, int64_t start, int64_t c
 int launch_value_histogram(hipStream_t s, const int32_t* values, int64_t n, int64_t n_bins,
                            unsigned long long* hist, unsigned long long* overflow);
 int launch_stream_order(hipStream_t s, const int32_t* tid, const int32_t* pos, int64_t n, unsigned long long* first_unsorted);
+// the BAM report (report.hip) into `out`, which the caller has zeroed on `s`: besst_dev_library_report's layout
+int launch_library_report(hipStream_t s, const besst_report_args& r, unsigned long long* out);
 
 struct ScoreArgs {
     const uint32_t* row;       // edge-table row per scored edge

@@ -351,6 +351,17 @@ class GraphContext(object):
         return (None if first.value < 0 else int(first.value)), (int(keys[0]), int(keys[1])), (int(keys[2]), int(keys[3]))
 
     @_timed
+    def library_report(self, isize_bins=32768):
+        """The BAM report of the resident records (besst_ctx_library_report: one pass over the eight columns; flag census,
+        counts per reference, mapq / qlen / |tlen| histograms, column digest) -> report.LibraryReport.  It only reads: the
+        planes, the side stream and their watermarks stay as they are."""
+        from . import report
+        words = np.zeros(report.report_words(self.n_contigs, int(isize_bins)), dtype=np.uint64)
+        _lib.check(self._lib.besst_ctx_library_report(self._ctx, int(isize_bins), _lib.ptr(words), words.shape[0]),
+                   'library_report')
+        return report.LibraryReport(words, self.n_contigs, int(isize_bins))
+
+    @_timed
     def metrics_sample(self, top_mask, orientation, min_mapq, read_len, want_isize=True):
         top = _lib.as_col(top_mask, np.uint8)
         isize = np.empty(SAMPLE_CAP, dtype=np.int32)

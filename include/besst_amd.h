@@ -460,6 +460,68 @@ int besst_ctx_metrics_sample(besst_ctx* ctx, const uint8_t* top_mask, int32_t or
 int besst_ctx_stream_order(besst_ctx* ctx, int64_t* first_unsorted, int32_t* first_key, int32_t* last_key);
 int besst_dev_stream_order(void* stream, int64_t n, const int32_t* tid, const int32_t* pos, int64_t* first_unsorted);
 
+/* The BAM report: what the resident record columns hold, counted over ALL records in one pass (csrc/report.hip) - the
+ * numbers of `samtools flagstat` and `samtools idxstats`, the mapq / aligned-length / insert-size distributions and a
+ * digest of the columns.  The result is besst_dev_library_report_words(n_refs, isize_bins) 64-bit words, every one an
+ * exact sum over the records (word 39 an xor), so reports of the slices of a stream add up to the report of the stream:
+ *   [0, 32)   flag census, row r at 2 r (QC-pass) and 2 r + 1 (QC-fail, flag & 0x200), rows in samtools flagstat's order:
+ *             0 total, 1 primary, 2 secondary, 3 supplementary, 4 duplicates, 5 primary duplicates, 6 mapped,
+ *             7 primary mapped, 8 paired in sequencing, 9 read1, 10 read2, 11 properly paired, 12 with itself and mate
+ *             mapped, 13 singletons, 14 with mate mapped to a different chr, 15 the same with mapQ >= 5.
+ *             secondary: 0x100; supplementary: 0x800 without 0x100; primary: neither; mapped: not 0x4; rows 8-15 count
+ *             primary records with 0x1: read1 0x40, read2 0x80, properly paired 0x2 and not 0x4, singletons 0x8 and not
+ *             0x4, itself and mate mapped neither 0x4 nor 0x8, different chr: of those, tid != mtid
+ *   32        unplaced: records with tid < 0            33   tid_out_of_range: records with tid >= n_refs
+ *   [34, 38)  pairs on one reference by class - innie, outie, tandem, other - each pair counted once, from its record with
+ *             primary, 0x1, 0x80, not 0x4, not 0x8, tid == mtid, 0 <= tid < n_refs.  rev = 0x10, mrev = 0x20:
+ *             tandem rev == mrev; else other tlen == 0; else innie (rev and tlen < 0) or (mrev and tlen > 0); else outie
+ *   38, 39    digest: sum (mod 2^64) and xor over the records of
+ *                 h = splitmix64(splitmix64(splitmix64(splitmix64(a) ^ b) ^ c) ^ mapq)
+ *                 a = (u32)tid | (u64)(u32)mtid << 32, b = (u32)pos | (u64)(u32)mpos << 32,
+ *                 c = (u32)tlen | (u64)flag << 32 | (u64)qlen << 48
+ *                 splitmix64(x): x += 0x9e3779b97f4a7c15; x = (x ^ x >> 30) * 0xbf58476d1ce4e5b9;
+ *                                x = (x ^ x >> 27) * 0x94d049bb133111eb; return x ^ x >> 31
+ *   [40, 296)          mapq histogram of the records without 0x4
+ *   [296, 65832)       qlen (stored aligned query length, clamped at 65535) histogram of the records without 0x4
+ *   [65832, + n_refs)  mapped[i]: records with tid == i without 0x4;  then n_refs words placed_unmapped[i]: with 0x4
+ *   then 3 x (isize_bins + 1) words: |tlen| histogram of the innie pairs, of the outie pairs, of the tandem pairs; bin
+ *   isize_bins of each counts |tlen| >= isize_bins (|tlen| in 64 bits: INT32_MIN lands there)
+ * besst_dev_library_report: caller-owned device columns at any element-aligned address (a slice of a stream), `out` a
+ * device buffer of out_words >= besst_dev_library_report_words(...) words that the call zeroes on `stream`; nothing is
+ * allocated or synchronised.  tid_bits: optional, the run-bit plane of the records (besst_lib_params.tid_bits); a hint
+ * only - the present kernel reads tid itself, the result never depends on it.  0 <= n_records < 2^32, 0 <= n_refs < 2^31,
+ * 1 <= isize_bins <= 2^20.
+ * besst_ctx_library_report: the same over the context's resident records (n_refs: the contig count of set_contigs), on the
+ * context's stream, fetched into out_host (out_words words).  It only reads: no watermark, plane or side stream moves. */
+#define BESST_REPORT_CENSUS 0
+#define BESST_REPORT_UNPLACED 32
+#define BESST_REPORT_TID_OUT_OF_RANGE 33
+#define BESST_REPORT_PAIR_CLASSES 34
+#define BESST_REPORT_DIGEST_SUM 38
+#define BESST_REPORT_DIGEST_XOR 39
+#define BESST_REPORT_MAPQ 40
+#define BESST_REPORT_QLEN 296
+#define BESST_REPORT_REFS 65832
+#define BESST_REPORT_MAX_ISIZE_BINS (1 << 20)
+typedef struct besst_report_args {
+    const int32_t* tid;
+    const int32_t* mtid;
+    const int32_t* pos;
+    const int32_t* mpos;
+    const int32_t* tlen;
+    const uint16_t* flag;
+    const uint8_t* mapq;
+    const uint16_t* qlen;
+    const void* tid_bits;
+    int64_t n_records;
+    int64_t n_refs;
+    int64_t isize_bins;
+    int64_t out_words;
+} besst_report_args;
+int64_t besst_dev_library_report_words(int64_t n_refs, int64_t isize_bins);
+int besst_dev_library_report(void* stream, const besst_report_args* args, uint64_t* out);
+int besst_ctx_library_report(besst_ctx* ctx, int64_t isize_bins, uint64_t* out_host, int64_t out_words);
+
 /* Count-per-value histogram of a sample on the device (input to find_bimodality.split_distribution,
  * find_bimodality.py:109-132).  hist_out has n_bins entries; values >= n_bins are counted in
  * *overflow. */
