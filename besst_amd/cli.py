@@ -1,9 +1,11 @@
 """Thin command-line counterpart of ``runBESST`` for the accelerated path only.
 
-    python -m besst_amd.cli -c contigs.fa -f lib1.bam [lib2.bam ...] -orientation fr [rf ...] -o outdir
+    python -m besst_amd.cli -c contigs.fa -f lib1.bam [lib2.sam ...] -orientation fr [rf ...] -o outdir
 
 Flag names and defaults follow runBESST:254-402 for everything the hot path reads (-m -s -T -k -r -e -z -z_min
---min_mapq -d -y --no_score -filter_contigs).  Per library it runs the BAM front-end, ``libmetrics.get_metrics`` and
+--min_mapq -d -y --no_score -filter_contigs).  A ``-f`` file is a BAM or SAM text as an aligner prints it - plain, BGZF or
+gzip, told by its content; the SAM lines are parsed on the GPU (bamio.ResidentSam), in any record order, and with
+``--gzip_on_gpu`` a gzip SAM is inflated there too.  Per library it runs the BAM / SAM front-end, ``libmetrics.get_metrics`` and
 ``CreateGraph.PE`` and writes Statistics.txt plus the scored edge tables of G and G' as TSV.  With ``--scaffolds -y`` it
 goes on like runBESST's loop without path extension: the graph is linearised, the paths become scaffolds, and every pass
 writes ``pass<n>/Scaffolds-pass<n>.fa`` with its ``.agp`` and ``.gff`` (the sequence work on the GPU).  With
@@ -27,7 +29,7 @@ Several GPUs of one node: launch the same command line under torchrun, one proce
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m besst_amd.cli -c ... -f ...
 
 Every rank ingests its slice of each BAM on its own GPU and takes part in the library scans and the graph build
-(besst_amd.sharded); rank 0 writes the outputs.
+(besst_amd.sharded); rank 0 writes the outputs.  The sharded input is BAM: a SAM file is refused there.
 """
 from __future__ import print_function
 
@@ -71,7 +73,8 @@ def build_parser():
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('-c', dest='contigfile', required=True,
                     help='contig FASTA, plain or gzip / BGZF compressed (told by its first bytes, not its name)')
-    ap.add_argument('-f', dest='bamfiles', nargs='+', required=True, help='one BAM per library')
+    ap.add_argument('-f', dest='bamfiles', nargs='+', required=True,
+                    help='one BAM or SAM file per library (SAM text plain, BGZF or gzip; told by content, not by name)')
     ap.add_argument('-o', dest='output', default='.', help='output directory')
     ap.add_argument('-orientation', dest='orientation', nargs='+', choices=['fr', 'rf'], required=True)
     ap.add_argument('-r', dest='readlen', type=int, nargs='+')
@@ -101,7 +104,8 @@ def build_parser():
                     help="with --fasta_on_gpu: a contig FASTA that is gzip but not BGZF (gzip's own output; one member or "
                          'several, as cat, gzip -c >> and multi-member compressors leave them) is inflated on '
                          'the GPU as well - block starts found by probing, chunks decoded side by side, CRC-32 checked; what '
-                         'the GPU does not take is read by zlib on the host as without the flag; needs --fasta_on_gpu')
+                         'the GPU does not take is read by zlib on the host as without the flag; needs --fasta_on_gpu.  '
+                         'It applies to a gzip-compressed SAM file of -f in the same way, with or without --fasta_on_gpu')
     ap.add_argument('--outputs_on_gpu', dest='outputs_on_gpu', action='store_true',
                     help='format info-pass<n>.agp / .gff on the GPU, and write repeats.fa / low_coverage_contigs.fa '
                          'from the sequence store in one go where the contigs live there (--fasta_on_gpu)')
@@ -125,6 +129,20 @@ def build_parser():
                     help="also run steps 1-4 of MakeScaffolds.Algorithm on a copy of G (isolated scaffolds, "
                          "score-based ambiguity removal, cycles) and write the surviving link edges")
     return ap
+
+
+def _input_format(path):
+    """'bam', 'sam' or 'sam.gz' (SAM text behind the gzip magic) of a -f file; a file that cannot be read counts as 'bam':
+    opening it says what is wrong."""
+    try:
+        fmt = bamio.sniff_format(path)
+        if fmt == 'sam':
+            with open(path, 'rb') as fh:
+                if fh.read(2) == bamio.GZIP_MAGIC:
+                    return 'sam.gz'
+        return fmt
+    except OSError:
+        return 'bam'
 
 
 def _per_lib(values, i):
@@ -268,10 +286,15 @@ def main(argv=None):
         sys.exit('--final_fasta needs --scaffolds: Scaffolds_pass<n>.fa is the scaffold FASTA followed by the repeats')
     if args.bgzf_outputs and not args.scaffolds:
         sys.exit('--bgzf_outputs needs --scaffolds: the file it compresses is the scaffold FASTA')
-    if args.gzip_on_gpu and not args.fasta_on_gpu:
+    formats = [_input_format(path) for path in args.bamfiles]
+    if args.gzip_on_gpu and not args.fasta_on_gpu and 'sam.gz' not in formats:
         sys.exit('--gzip_on_gpu needs --fasta_on_gpu: it is the sequence store that reads the compressed file on the GPU')
     if args.max_contig_overlap < 0 or args.max_contig_overlap > GO.MAX_CONTIG_OVERLAP_LIMIT:
         sys.exit('-max_contig_overlap must lie in 0..%d' % GO.MAX_CONTIG_OVERLAP_LIMIT)
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        for path, fmt in zip(args.bamfiles, formats):
+            if fmt in ('sam', 'sam.gz'):                         # every rank alike, before any collective
+                sys.exit(bamio.SHARDED_SAM_MESSAGE % path)
     rank, joined = join_process_group()
     try:
         return _run(args, rank)
@@ -334,7 +357,8 @@ def _run(args, rank):
         t0 = time()
         # straight to HBM: inflate + record decode on the GPU (any BGZF block layout)
         # (under torchrun: this rank's slice of the file, on this rank's GPU)
-        records = bamio.open_bam(bam, threads=args.threads)
+        # (--gzip_on_gpu also applies to a gzip SAM; the keyword goes along only when the flag is given)
+        records = bamio.open_bam(bam, threads=args.threads, **({'gzip_on_gpu': True} if args.gzip_on_gpu else {}))
         print('Time elapsed reading %s (%d records): %s' % (bam, len(records), time() - t0), file=Information)
         param.contig_index = dict(enumerate(records.references))
         if args.bam_report:

@@ -179,6 +179,8 @@ void besst_ctx_destroy(besst_ctx* c) {
     c->row_sum.release(); c->row_sum_sq.release(); c->obs_lo.release(); c->obs_hi.release();
     c->ws.release(); c->small.release(); c->top_mask.release(); c->sample_a.release();
     c->sample_b.release(); c->aux.release(); c->ln_tables.release();
+    c->sam_slots.release(); c->sam_rows.release(); c->sam_pool.release(); c->sam_off.release(); c->sam_ws.release();
+    c->sam_head.release();
     if (c->side_stream) {
         (void)hipStreamSynchronize(c->side_stream);
         (void)hipStreamDestroy(c->side_stream);

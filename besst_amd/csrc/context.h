@@ -86,6 +86,18 @@ struct besst_ctx {
     besst::DevBuf<double> ln_tables;
     double ln_mu = 0.0, ln_sigma = 0.0;
     int64_t ln_x_max = 0;
+    // SAM text ingest (sam.hip): the reference table of besst_ctx_set_sam_references (slots, the names end to end, their
+    // offsets), the tile scratch and line rows of a chunk, the head arrays of the first records
+    besst::DevBuf<uint32_t> sam_slots, sam_rows;
+    besst::DevBuf<uint8_t> sam_pool;
+    besst::DevBuf<int64_t> sam_off;
+    besst::DevBuf<char> sam_ws, sam_head;
+    uint32_t sam_cap = 0;
+    int64_t sam_refs = 0;
+    // besst_ctx_sam_expect_text: the record text announced for the file being pushed, what of it has come, its records
+    int64_t sam_expect_bytes = 0, sam_seen_bytes = 0, sam_file_records = 0;
+    bool sam_timing = false;                // besst_ctx_sam_pass_times: events around the four passes of every push
+    double sam_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 namespace besst {

@@ -1170,6 +1170,59 @@ int besst_dev_bgzf_deflate(void* stream, const void* src, int64_t n_bytes, int32
 int besst_bgzf_deflate_device(int device, const void* src, size_t n_bytes, int32_t block_payload, int32_t with_eof, void* out,
                               size_t out_cap, size_t* out_len);
 
+/* ---- SAM text -> the context's record columns (csrc/sam.hip; the per-record rules: csrc/sam_core.h) ---------------------
+ * A chunk of record lines in HBM - it begins at a line start and ends at a line end or at the end of the file; 16-byte
+ * aligned, below 2^32 - 16 bytes, with 16 readable bytes behind its end - is parsed on the device and its records are
+ * appended to the context's columns with exactly what the BAM of the same records gives.  '\n' ends a line, a '\r' in
+ * front of it belongs to the terminator, a last line without '\n' is a line.  A record is the first eleven tab-separated
+ * fields: FLAG [0-9]+ <= 65535; RNAME '*' -> -1, else its row among the references; POS / PNEXT [0-9]+ <= 2^31 - 1, stored
+ * less one; MAPQ <= 255; RNEXT '=' -> tid, '*' -> -1; TLEN -?[0-9]+ within int32; l_seq the length of SEQ ('*': 0); qlen /
+ * alen / rlen from CIGAR (operations MIDNSHP=X, counts below 2^28, '*': none) and l_seq as besst_bam_read_records derives
+ * them.  QUAL and the optional fields are never read.
+ *   besst_ctx_set_sam_references   the header's names end to end (name r: names[name_off[r]] .. names[name_off[r + 1]]),
+ *                                  once per file: an open-addressing table of >= 2 n_ref slots is built on the host and
+ *                                  uploaded with the names.  BESST_ERR_ARG: an empty or a repeated name.
+ *   besst_dev_sam_workspace_bytes  tile scratch the context keeps for a chunk of that size (the rows, 20 bytes per
+ *                                  line, come on top); 0: tile_bytes or text_bytes not accepted.  Needs no GPU.
+ *   besst_ctx_push_sam_text        tile_bytes: 0 = 16384, else a multiple of 1024 in 1024..65536.  Kernels run on `stream`
+ *                                  (null: the context's); the call returns when the chunk is decoded.  info[0] records of
+ *                                  the chunk, [1] records whose qlen was saturated at 65535, [2] the smallest file offset
+ *                                  (file_offset + offset in the chunk) of the first byte of a line that cannot be read
+ *                                  (-1: none), [3] that line's BESST_SAM_* reason.  With an error the records of the chunk
+ *                                  are NOT appended.  head_rlen / head_alen / head_qlen (host, head_records entries): the
+ *                                  values of the context's first head_records records, filled on across calls.
+ *                                  The mate / run planes and the candidate side stream are not written: the watermarks
+ *                                  stay where they are, as after besst_ctx_push_records.
+ *                                  BESST_ERR_ARG without touching the device: a null context, a tile_bytes out of range,
+ *                                  a misaligned text.
+ *   besst_ctx_sam_expect_text      optional, before a file's first chunk: the bytes of record text the pushes that follow
+ *                                  will bring in all.  When the columns have to grow they then grow once, to what the rest
+ *                                  of that text needs at the records per byte seen so far (plus 3 %; at most a record per
+ *                                  22 bytes), instead of chunk after chunk; without it they double.
+ *   besst_ctx_sam_pass_times       measurement (tools/time_sam_ingest.py): ms[0..4), where given, receives the device time
+ *                                  of the flags, state, index (with the rows' memset) and decode passes summed over the
+ *                                  pushes since the last call, by events; the sums are cleared and the events switched on
+ *                                  or off for the pushes that follow. */
+#define BESST_SAM_INFO_WORDS 4
+#define BESST_SAM_FEW_FIELDS 1
+#define BESST_SAM_EMPTY_LINE 2
+#define BESST_SAM_HEADER_LINE 3
+#define BESST_SAM_BAD_FLAG 4
+#define BESST_SAM_BAD_POS 5
+#define BESST_SAM_BAD_MAPQ 6
+#define BESST_SAM_BAD_PNEXT 7
+#define BESST_SAM_BAD_TLEN 8
+#define BESST_SAM_BAD_RNAME 9
+#define BESST_SAM_BAD_RNEXT 10
+#define BESST_SAM_BAD_CIGAR 11
+int besst_ctx_set_sam_references(besst_ctx* ctx, const uint8_t* names, const int64_t* name_off, int64_t n_ref);
+size_t besst_dev_sam_workspace_bytes(int64_t text_bytes, int64_t tile_bytes);
+int besst_ctx_push_sam_text(besst_ctx* ctx, void* stream, const uint8_t* text, int64_t text_bytes, int64_t file_offset,
+                            int64_t tile_bytes, int64_t head_records, int32_t* head_rlen, int32_t* head_alen,
+                            uint16_t* head_qlen, int64_t* info);
+int besst_ctx_sam_expect_text(besst_ctx* ctx, int64_t text_bytes);
+int besst_ctx_sam_pass_times(besst_ctx* ctx, int enable, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
