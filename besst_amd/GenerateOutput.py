@@ -641,14 +641,16 @@ def gzip_member_capacity(comp_bytes):
     return int(comp_bytes) // 256 + 4096
 
 
-def _upload_gzip_device(torch, dev, path, chunk_bytes, stats):
+def _upload_gzip_device(torch, dev, path, chunk_bytes, stats, max_text=None):
     """A file that is a series of gzip members, inflated on the device (csrc/gzip_stream.hip): the compressed file goes up
     as it is (_upload_file); besst_dev_gzip_members_plan finds the chunks and the members that can be decoded side by side
     and the text's size - the one read from the device in the middle -, besst_dev_gzip_members_inflate decodes, resolves
     the windows and checks every member's CRC-32.
     -> (text, n) as _upload_file, or None with stats['status'] saying why (and, where the device names one,
     stats['bad_member'] and stats['bad_member_offset']): the caller reads the file on the host, which also words the error
-    where the file is damaged.  Every temporary is let go before that."""
+    where the file is damaged.  Every temporary is let go before that.  ``max_text``: a text of more bytes than this is not
+    inflated - None with stats['status'] 'too_large', known from the plan before the text buffer is asked for (bamio's SAM
+    reader then streams the file)."""
     lib = _lib.load()
     p = _C.c_void_p
     size = os.path.getsize(path)
@@ -682,6 +684,9 @@ def _upload_gzip_device(torch, dev, path, chunk_bytes, stats):
         if status:
             bad_member(words)
             return None
+        if max_text is not None and n > max_text:
+            stats['status'] = 'too_large'
+            return None
         ws_bytes = lib.besst_dev_gzip_members_inflate_workspace_bytes(n, live, members)
         if not ws_bytes:
             stats['status'] = 'file_size'
@@ -703,10 +708,11 @@ def _upload_gzip_device(torch, dev, path, chunk_bytes, stats):
         return None
 
 
-def _gzip_members(fh, piece=1 << 20):
+def _gzip_members(fh, piece=1 << 20, base=0):
     """The inflated bytes of a file of gzip members, in pieces of at most ``piece`` bytes.  FastaError: the offset of the
-    member that zlib does not inflate (its data, CRC-32 or length), that the file's end cuts, or that is no gzip member."""
-    pending, pos, d, member_at = b'', 0, None, 0
+    member that zlib does not inflate (its data, CRC-32 or length), that the file's end cuts, or that is no gzip member.
+    ``base``: where in the file ``fh`` stands (the members behind a chain of BGZF blocks)."""
+    pending, pos, d, member_at = b'', int(base), None, int(base)
     while True:
         if not pending:
             pending = fh.read(piece)

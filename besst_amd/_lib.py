@@ -281,6 +281,7 @@ _SIGNATURES = {
     'besst_ctx_set_sam_references': (C.c_int, [_P, _P, _P, C.c_int64]),
     'besst_dev_sam_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
     'besst_ctx_sam_expect_text': (C.c_int, [_P, C.c_int64]),
+    'besst_dev_sam_lines': (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, _P]),
     'besst_ctx_sam_pass_times': (C.c_int, [_P, C.c_int, _P]),
     'besst_ctx_push_sam_text': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P]),
 }

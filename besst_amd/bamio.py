@@ -6,8 +6,10 @@ device (or on host threads); the decoded columns are the same SoA layout the dev
 
 SAM text - what ``bwa mem``, ``bowtie2`` and ``minimap2`` print - is read by :class:`ResidentSam`: the header on the
 host, the record lines parsed on the device (csrc/sam.hip) into the same columns, with the values the BAM of the same
-records gives.  The file may be plain, BGZF or gzip; :func:`open_bam` tells the format by content, never by name.  The
-record loop is exact on any record order, so an aligner's read-ordered SAM goes straight in.
+records gives.  The file may be plain, BGZF or gzip; :func:`open_bam` tells the format by content, never by name.  Every
+form is streamed in chunks - BGZF is inflated on the device and cut at line ends there (besst_dev_sam_lines), other gzip
+is inflated by zlib on the host -, so the file may be of any size.  The record loop is exact on any record order, so an
+aligner's read-ordered SAM goes straight in.
 """
 import os
 import zlib
@@ -177,6 +179,7 @@ SAM_CHUNK_BYTES = 64 << 20               # ResidentSam streams a plain file thro
 SAM_DEFAULT_TILE = 16384                 # csrc/sam.hip: the tile of tile_bytes = 0
 SAM_TEXT_PAD = 64                        # readable bytes behind a chunk's end in HBM
 SAM_MAX_TEXT = (1 << 32) - 17            # one parsed chunk (besst_ctx_push_sam_text)
+BGZF_MAX_ISIZE = 65536                   # a BGZF block inflates to this much at most
 HEAD_RECORDS = 1000
 
 
@@ -235,9 +238,12 @@ class ResidentSam(object):
 
     A plain file: the header is read on the host, the record lines stream through two pinned buffers of ``chunk_bytes``
     (a multiple of ``tile_bytes``), each chunk cut at its last line end and the tail carried to the front of the next one -
-    only the columns stay resident, the file may be larger than HBM.  A file that begins with the gzip magic is brought to
-    HBM whole by GenerateOutput's uploaders (BGZF inflated on the device; gzip by zlib on the host, or on the device with
-    ``gzip_on_gpu``) and parsed there; its inflated text has to fit beside the columns, and below 4 GiB.
+    only the columns stay resident, the file may be larger than HBM.  A file that begins with the gzip magic is streamed as
+    well, ``chunk_bytes`` of inflated text a round: BGZF is inflated on the device into two text buffers, cut at
+    its last line end by the device (``inflate`` 'device'; ``inflate_stats``: rounds, windows, host_rounds, host_from);
+    other gzip is inflated by zlib on the host and goes through the plain file's loop ('host').  With ``gzip_on_gpu`` a gzip
+    file whose text is below 4 GiB and fits in HBM is inflated there whole and parsed as one chunk ('device_gzip'); else it
+    is streamed on the host and ``inflate_stats['status']`` says why ('too_large', 'allocation', or the device's reason).
 
     The mate / run planes and the candidate side stream are not written while decoding: ``layout_state()`` shows the
     watermarks at 0 and the first build runs the makers, as after a host push.  SamError: a line that cannot be read (the
@@ -265,7 +271,7 @@ class ResidentSam(object):
             compressed = fh.read(2) == GZIP_MAGIC
         try:
             if compressed:
-                self._read_compressed(device, int(device_index), bool(gzip_on_gpu))
+                self._read_compressed(device, int(device_index), bool(gzip_on_gpu), chunk)
             else:
                 self._read_plain(device, int(device_index), chunk)
         except Exception:
@@ -311,94 +317,368 @@ class ResidentSam(object):
 
     # ---- a plain file: chunks through two pinned buffers -----------------------------------------------------------------
     def _read_plain(self, device, device_index, chunk):
-        import torch
         with open(self.path, 'rb') as fh:
             header, at = _read_plain_header(fh)
             self._open_context(device, device_index, header)
-            dev = torch.device('cuda', device_index)
-            step = self._tile or SAM_DEFAULT_TILE
-            left = os.fstat(fh.fileno()).st_size - at             # (a file smaller than a chunk needs no more than its size)
-            chunk = min(chunk, max(step, -(-left // step) * step))
-            _lib.check(self._lib.besst_ctx_sam_expect_text(self.ctx._ctx, int(left)), 'sam_expect_text')
-            with torch.cuda.device(dev):
-                h_buf = [torch.empty(chunk, dtype=torch.uint8).pin_memory() for _ in range(2)]
-                # (not zeroed: the parser masks every byte behind a chunk's end, the pad only has to be readable - and a
-                # fill on the current stream would have to be ordered in front of the first copies on the side stream)
-                d_buf = [torch.empty(chunk + SAM_TEXT_PAD, dtype=torch.uint8, device=dev) for _ in range(2)]
-                views = [memoryview(b.numpy()) for b in h_buf]
-                copy = torch.cuda.Stream(dev)
-                copy.wait_stream(torch.cuda.current_stream(dev))
-                lines_before = len(header)
-                pending = None                                   # (slot, bytes, file offset, copied event) of the chunk in flight
-                carry, slot, eof = 0, 0, False
-
-                def parse(job):
-                    nonlocal lines_before
-                    j_slot, j_bytes, j_off, j_done = job
-                    torch.cuda.current_stream(dev).wait_event(j_done)
-                    info = self._push(torch.cuda.current_stream(dev).cuda_stream, d_buf[j_slot].data_ptr(), j_bytes, j_off)
-                    if info[2] >= 0:
-                        rel = int(info[2]) - j_off
-                        line = lines_before + 1 + int(np.count_nonzero(h_buf[j_slot].numpy()[:rel] == 10))
-                        raise _sam_error(self.path, info, line, False)
-                    lines_before += int(info[0])
-
-                try:
-                    while not eof:
-                        view = views[slot]
-                        room = chunk - carry
-                        got = _read_full(fh, view[carry:chunk]) if room else 0
-                        have = carry + got
-                        eof = got < room
-                        if have == 0:
-                            break
-                        cut = have if eof else _last_line_end(view, have)
-                        if cut == 0:
-                            if pending is not None:
-                                parse(pending)                   # (an earlier line's error comes first)
-                            raise SamError('%s: the line at byte %d is longer than chunk_bytes = %d; raise chunk_bytes'
-                                           % (self.path, at, chunk), at, None, 'line longer than a chunk')
-                        with torch.cuda.stream(copy):
-                            d_buf[slot][:cut].copy_(h_buf[slot][:cut], non_blocking=True)
-                            done = torch.cuda.Event()
-                            done.record(copy)
-                        self.ingest.bytes_h2d += cut
-                        job = (slot, cut, at, done)
-                        if pending is not None:
-                            parse(pending)                       # chunk c - 1 is parsed while chunk c crosses
-                        pending = job
-                        other = views[1 - slot]                  # (its chunk was parsed just now: the buffer is free)
-                        carry = have - cut
-                        other[:carry] = view[cut:have]
-                        at += cut
-                        slot = 1 - slot
-                    if pending is not None:
-                        parse(pending)
-                finally:
-                    copy.synchronize()                           # no copy is in flight when the buffers are let go, error or not
+            left = os.fstat(fh.fileno()).st_size - at
+            at = self._stream_lines(device_index, fh, len(header), at, left, chunk, False)
         self.ingest.inflated_bytes = at
 
-    # ---- a compressed file: the text is inflated into HBM whole and parsed in place ---------------------------------------
-    def _read_compressed(self, device, device_index, gzip_on_gpu):
+    def _stream_lines(self, device_index, fh, lines_before, at, left, chunk, compressed):
+        """The record lines that ``fh.readinto`` brings (a plain file behind its header, or the inflated bytes of gzip
+        members), in chunks through two pinned buffers, into the open context.  ``at``: the text offset of the first of
+        them, ``lines_before``: the lines in front; ``left``: their bytes where known (None: not known - the chunk is not
+        made smaller and the columns are not announced).  -> the text offset behind the last byte."""
+        import torch
+        dev = torch.device('cuda', device_index)
+        step = self._tile or SAM_DEFAULT_TILE
+        if left is not None:                                 # (a file smaller than a chunk needs no more than its size)
+            chunk = min(chunk, max(step, -(-left // step) * step))
+            _lib.check(self._lib.besst_ctx_sam_expect_text(self.ctx._ctx, int(left)), 'sam_expect_text')
+        with torch.cuda.device(dev):
+            h_buf = [torch.empty(chunk, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            # (not zeroed: the parser masks every byte behind a chunk's end, the pad only has to be readable - and a
+            # fill on the current stream would have to be ordered in front of the first copies on the side stream)
+            d_buf = [torch.empty(chunk + SAM_TEXT_PAD, dtype=torch.uint8, device=dev) for _ in range(2)]
+            views = [memoryview(b.numpy()) for b in h_buf]
+            copy = torch.cuda.Stream(dev)
+            copy.wait_stream(torch.cuda.current_stream(dev))
+            pending = None                                # (slot, bytes, file offset, copied event) of the chunk in flight
+            carry, slot, eof = 0, 0, False
+
+            def parse(job):
+                nonlocal lines_before
+                j_slot, j_bytes, j_off, j_done = job
+                torch.cuda.current_stream(dev).wait_event(j_done)
+                info = self._push(torch.cuda.current_stream(dev).cuda_stream, d_buf[j_slot].data_ptr(), j_bytes, j_off)
+                if info[2] >= 0:
+                    rel = int(info[2]) - j_off
+                    line = lines_before + 1 + int(np.count_nonzero(h_buf[j_slot].numpy()[:rel] == 10))
+                    raise _sam_error(self.path, info, line, compressed)
+                lines_before += int(info[0])
+
+            try:
+                while not eof:
+                    view = views[slot]
+                    room = chunk - carry
+                    got = _read_full(fh, view[carry:chunk]) if room else 0
+                    have = carry + got
+                    eof = got < room
+                    if have == 0:
+                        break
+                    cut = have if eof else _last_line_end(view, have)
+                    if cut == 0:
+                        if pending is not None:
+                            parse(pending)                   # (an earlier line's error comes first)
+                        raise SamError('%s: the line at byte %d is longer than chunk_bytes = %d; raise chunk_bytes'
+                                       % (self.path, at, chunk), at, None, 'line longer than a chunk')
+                    with torch.cuda.stream(copy):
+                        d_buf[slot][:cut].copy_(h_buf[slot][:cut], non_blocking=True)
+                        done = torch.cuda.Event()
+                        done.record(copy)
+                    self.ingest.bytes_h2d += cut
+                    job = (slot, cut, at, done)
+                    if pending is not None:
+                        parse(pending)                       # chunk c - 1 is parsed while chunk c crosses
+                    pending = job
+                    other = views[1 - slot]                  # (its chunk was parsed just now: the buffer is free)
+                    carry = have - cut
+                    other[:carry] = view[cut:have]
+                    at += cut
+                    slot = 1 - slot
+                if pending is not None:
+                    parse(pending)
+            finally:
+                copy.synchronize()                           # no copy is in flight when the buffers are let go, error or not
+        return at
+
+    # ---- a compressed file: inflated and parsed chunk by chunk --------------------------------------------------------------
+    def _compressed_error(self, message, offset):
+        """(the offset is the damaged block's or member's in the COMPRESSED file - the text was never inflated that far)"""
+        return SamError('%s: %s (byte %d of the compressed file, not of the inflated text)'
+                        % (self.path, message.replace('compressed FASTA file', 'compressed SAM file'), offset),
+                        offset, None, 'compressed data')
+
+    def _read_compressed(self, device, device_index, gzip_on_gpu, chunk):
         from . import GenerateOutput as GO
         torch, dev = GO._torch_device(device_index)
-        stats = dict(chunks=0, candidates=0, live=0, text_bytes=0, status=None)
-        with torch.cuda.device(dev):
-            try:
-                text, n, self.inflate = GO._upload_gzip_file(torch, dev, self.path, None,
-                                                             GO.GZIP_CHUNK_BYTES if gzip_on_gpu else None, stats)
-            except GO.FastaError as exc:
-                # (the uploaders word their errors for the contig file; the offset is the damaged block's or member's in
-                # the COMPRESSED file - the text was never inflated that far)
-                raise SamError('%s: %s (byte %d of the compressed file, not of the inflated text)'
-                               % (self.path, str(exc).replace('compressed FASTA file', 'compressed SAM file'), exc.offset),
-                               exc.offset, None, 'compressed data')
-            except torch.cuda.OutOfMemoryError:
-                raise MemoryError('%s: the inflated SAM text does not fit in HBM beside the record columns; inflate the file '
-                                  'first - a plain SAM file is streamed in chunks' % self.path)
+        n_blocks, total, end, size = GO.bgzf_walk(self.path)
+        try:
+            if end > 0:                                          # the file begins with a chain of BGZF blocks
+                with torch.cuda.device(dev):
+                    self._read_bgzf(device, device_index, torch, dev, chunk, total, end, size)
+                return
+            stats = dict(chunks=0, candidates=0, live=0, text_bytes=0, status=None)
             self.inflate_stats = stats
-            self.ingest.bytes_h2d = os.path.getsize(self.path)
-            self.ingest.inflated_bytes = n
+            if gzip_on_gpu:
+                with torch.cuda.device(dev):
+                    got = GO._upload_gzip_device(torch, dev, self.path, GO.GZIP_CHUNK_BYTES, stats, max_text=SAM_MAX_TEXT)
+                if got is not None:
+                    self.inflate = 'device_gzip'
+                    self.ingest.bytes_h2d = size
+                    self.ingest.inflated_bytes = got[1]
+                    self._parse_resident(device, device_index, torch, dev, got[0], got[1])
+                    return
+            self.inflate = 'host'
+            with open(self.path, 'rb') as fh:
+                self._read_members(device, device_index, fh, 0, b'', [], True, 0, chunk)
+        except GO.FastaError as exc:                             # (the uploaders word their errors for the contig file)
+            raise self._compressed_error(str(exc), exc.offset)
+
+    def _read_members(self, device, device_index, fh, base, prefix, header, in_header, at, chunk):
+        """The gzip members from byte ``base`` of the file on, inflated by zlib on the host and streamed as a plain file is.
+        ``prefix``: text in front of their output (what a chain of BGZF blocks left behind its last cut), ``header``: the
+        header lines read so far, ``in_header``: the header may go on, ``at``: the text offset of the prefix's first byte."""
+        src = _MemberStream(fh, base, prefix)
+        if in_header:
+            more, size = src.header_lines()
+            header, at = header + more, at + size
+        if self.ctx is None:
+            self._open_context(device, device_index, header)
+        at = self._stream_lines(device_index, src, len(header) + int(self.ingest.records), at, None, chunk, True)
+        self.ingest.inflated_bytes = at
+
+    def _read_bgzf(self, device, device_index, torch, dev, chunk, total, end, size):
+        """BGZF text, round by round.  A round: the text buffer holds the carry - the bytes behind the last
+        cut - at offset 0; whole blocks are appended in file order while fewer than ``chunk`` bytes are held; they are
+        inflated at their places (besst_dev_bgzf_inflate), the cutter (besst_dev_sam_lines) finds the last line end or the
+        header's end, and one read brings its answers and the first bad block to the host.  The text up to the cut is
+        pushed, the rest is copied to the front of the other buffer.  The compressed bytes come through two pinned and two
+        device windows; the next window is read and sent while the round's kernels run."""
+        import ctypes as C
+        from . import GenerateOutput as GO
+        lib, p = self._lib, C.c_void_p
+        step = self._tile or SAM_DEFAULT_TILE
+        chunk = min(chunk, (SAM_MAX_TEXT - BGZF_MAX_ISIZE) // step * step)
+        if end == size:                                          # (a file smaller than a chunk needs no more than its text)
+            chunk = min(chunk, max(step, -(-total // step) * step))
+        self.inflate = 'device'
+        stats = self.inflate_stats = dict(rounds=0, windows=0, host_rounds=0, host_from=None, status=None)
+        main = torch.cuda.current_stream(dev)
+        per_launch = int(GO.BLOCKS_PER_LAUNCH)
+        launch_cap = min(per_launch * BGZF_MAX_ISIZE, chunk + BGZF_MAX_ISIZE)
+        ws_bytes = lib.besst_dev_bgzf_inflate_workspace_bytes(per_launch, launch_cap)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        # (not zeroed: the cutter and the parser mask every byte behind the text's end, the pad only has to be readable)
+        t_buf = [torch.empty(chunk + BGZF_MAX_ISIZE + SAM_TEXT_PAD, dtype=torch.uint8, device=dev) for _ in range(2)]
+        status = torch.full((5,), -1, dtype=torch.int64, device=dev)      # the cutter's four words, the first bad block
+        cap = min(max(GO.BGZF_MAX_BLOCK, min(int(GO.UPLOAD_CHUNK), chunk)), max(GO.BGZF_MAX_BLOCK, -(-end // 16) * 16))
+        w_host = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        w_dev = [torch.zeros(cap + GO.BGZF_COMP_PAD, dtype=torch.uint8, device=dev) for _ in range(2)]
+        w_view = [memoryview(b.numpy()) for b in w_host]
+        desc_type = np.dtype([('src_off', '<u4'), ('src_len', '<u4'), ('dst_lo', '<u4'), ('dst_hi', '<u4'), ('dst_len', '<u4'),
+                              ('crc', '<u4')])
+        assert desc_type.itemsize == GO.BGZF_DESC_BYTES
+        scan_cap = cap // 26 + 2                                 # (a block is 28 bytes at least)
+        scanned = np.zeros(scan_cap, dtype=desc_type)
+        d_cap = max(2 * per_launch, 8192)                        # descriptors staged per round (more: a wait in the middle)
+        h_desc = torch.empty(d_cap * GO.BGZF_DESC_BYTES, dtype=torch.uint8).pin_memory()
+        d_desc = torch.empty(d_cap * GO.BGZF_DESC_BYTES, dtype=torch.uint8, device=dev)
+        h_desc_np = h_desc.numpy().view(desc_type)
+        copy = torch.cuda.Stream(dev)
+        copy.wait_stream(main)
+        sent, inflated_ev = [None, None], [None, None]
+        state = dict(file_at=0, cut_block=b'', w_slot=0, blocks=0)
+        n_got, comp, infl = C.c_int64(0), C.c_size_t(0), C.c_int64(0)
+
+        def more_windows():
+            return state['file_at'] < end or len(state['cut_block']) > 0
+
+        def load_window(fh):
+            """the next window of the chain: read, its blocks found, sent on the side stream -> its table"""
+            slot = state['w_slot']
+            if sent[slot] is not None:
+                sent[slot].synchronize()                         # the buffer's last copy has left it
+            view, have = w_view[slot], len(state['cut_block'])
+            first_at = state['file_at'] - have
+            view[:have] = state['cut_block']
+            want = min(cap - have, end - state['file_at'])
+            got = _read_full(fh, view[have:have + want])
+            if got != want:
+                raise IOError('%s ended %d bytes early' % (self.path, want - got))
+            have, state['file_at'] = have + got, state['file_at'] + got
+            _lib.check(lib.besst_bgzf_scan_chunk(p(w_host[slot].data_ptr()), have, 0, 1 if state['file_at'] < end else 0, scan_cap, 0,
+                                                 p(scanned.ctypes.data), C.byref(n_got), C.byref(comp), C.byref(infl)),
+                       'besst_bgzf_scan_chunk')
+            n = int(n_got.value)
+            if not n:
+                raise IOError('%s changed while it was read' % self.path)
+            d = scanned[:n]
+            src_off, src_len = d['src_off'].astype(np.int64), d['src_len'].astype(np.int64)
+            starts = np.empty(n, dtype=np.int64)                 # where every block begins in the file
+            starts[0] = first_at
+            starts[1:] = first_at + src_off[:-1] + src_len[:-1] + 8
+            tab = dict(slot=slot, n=n, at=0, src_off=d['src_off'].copy(), src_len=d['src_len'].copy(), isize=d['dst_len'].copy(),
+                       crc=d['crc'].copy(), cum=np.cumsum(d['dst_len'].astype(np.int64)), starts=starts,
+                       payload_at=first_at + src_off)
+            state['cut_block'] = bytes(view[comp.value:have])
+            with torch.cuda.stream(copy):
+                if inflated_ev[slot] is not None:
+                    copy.wait_event(inflated_ev[slot])           # the launches that last read this device window
+                w_dev[slot][:comp.value].copy_(w_host[slot][:comp.value], non_blocking=True)
+                sent[slot] = torch.cuda.Event()
+                sent[slot].record(copy)
+            self.ingest.bytes_h2d += int(comp.value)
+            state['w_slot'] = 1 - slot
+            stats['windows'] += 1
+            return tab
+
+        header, in_header, lines_before = [], True, 0
+        text_at, carry, slot = 0, 0, 0
+        cur, nxt = None, None
+        tail = end < size                                        # something that is no BGZF block follows the chain
+        try:
+            with open(self.path, 'rb', buffering=0) as fh:
+                while True:
+                    # -- the round's blocks: launched as they are taken
+                    held, first_block, used, taken = carry, state['blocks'], 0, []
+                    while held < chunk:
+                        if cur is None or cur['at'] == cur['n']:
+                            if nxt is not None:
+                                cur, nxt = nxt, None
+                            elif more_windows():
+                                cur = load_window(fh)
+                            else:
+                                cur = None
+                                break
+                            continue
+                        cum, a = cur['cum'], cur['at']
+                        before = int(cum[a - 1]) if a else 0
+                        j = min(cur['n'], int(np.searchsorted(cum, before + chunk - held, side='left')) + 1)
+                        main.wait_event(sent[cur['slot']])
+                        while a < j:
+                            before = int(cum[a - 1]) if a else 0
+                            b = min(j, a + per_launch, int(np.searchsorted(cum, before + launch_cap, side='right')))
+                            b = max(b, a + 1)
+                            nb, nbytes = b - a, int(cum[b - 1]) - before
+                            if used + nb > d_cap:
+                                main.synchronize()               # the staged descriptors have been read
+                                used = 0
+                            d = h_desc_np[used:used + nb]
+                            d['src_off'], d['src_len'] = cur['src_off'][a:b], cur['src_len'][a:b]
+                            d['dst_len'], d['crc'], d['dst_hi'] = cur['isize'][a:b], cur['crc'][a:b], 0
+                            d['dst_lo'] = (cum[a:b] - cur['isize'][a:b].astype(np.int64) - before).astype(np.uint32)
+                            lo, hi = used * GO.BGZF_DESC_BYTES, (used + nb) * GO.BGZF_DESC_BYTES
+                            d_desc[lo:hi].copy_(h_desc[lo:hi], non_blocking=True)
+                            _lib.check(lib.besst_dev_bgzf_inflate(p(main.cuda_stream), p(w_dev[cur['slot']].data_ptr()),
+                                                                  p(d_desc.data_ptr() + lo), nb, state['blocks'], nbytes,
+                                                                  p(t_buf[slot].data_ptr() + held), p(ws.data_ptr()), ws_bytes,
+                                                                  p(status.data_ptr() + 32)), 'besst_dev_bgzf_inflate')
+                            taken.append((cur, a, b, held))
+                            used, held, a = used + nb, held + nbytes, b
+                            state['blocks'] += nb
+                        cur['at'] = j
+                        inflated_ev[cur['slot']] = torch.cuda.Event()
+                        inflated_ev[cur['slot']].record(main)
+                    chain_end = (cur is None or cur['at'] == cur['n']) and nxt is None and not more_windows()
+                    eof = chain_end and not tail
+                    if held == 0:
+                        break
+                    stats['rounds'] += 1
+                    # -- the next window is read and sent while the round's kernels run
+                    if nxt is None and more_windows() and (cur is None or cur['slot'] != state['w_slot']):
+                        nxt = load_window(fh)
+                    words = self._cut(main, t_buf[slot], held, in_header, 0, status)
+                    if words[4] != -1:
+                        block, reason = int(words[4]) >> 8, int(words[4]) & 0xff
+                        k = block - first_block
+                        for tab, a, b, _ in taken:
+                            if k < b - a:
+                                bad_at = int(tab['starts'][a + k])
+                                break
+                            k -= b - a
+                        if reason in (GO.BGZF_BAD_SIZE, GO.BGZF_BAD_CRC):
+                            raise self._compressed_error(
+                                'the BGZF block at byte %d of the compressed SAM file (block %d) is damaged: %s' % (
+                                    bad_at, block, 'its CRC-32 is not that of its inflated bytes' if reason == GO.BGZF_BAD_CRC
+                                    else 'it does not inflate to ISIZE bytes'), bad_at)
+                        # the device kernel does not take a block's DEFLATE data: the round's blocks by zlib on the host
+                        self._host_round(torch, dev, taken, t_buf[slot])
+                        stats['host_rounds'] += 1
+                        status[4:].fill_(-1)
+                        words = self._cut(main, t_buf[slot], held, in_header, 0, status)
+                    last_end, header_end = int(words[0]), int(words[1])
+                    if in_header and header_end != 0:
+                        if header_end < 0:                       # header lines, the last one perhaps not whole
+                            take = held if eof else last_end
+                        else:
+                            take, in_header = header_end, header_end == held
+                        if take == 0 and held >= chunk:
+                            raise self._long_line(text_at, chunk)
+                        header += _split_lines(t_buf[slot][:take].cpu().numpy().tobytes())
+                    else:
+                        if in_header:
+                            in_header = False
+                        if self.ctx is None:
+                            self._open_context(device, device_index, header)
+                            lines_before = len(header)
+                            if not tail:                         # an estimate: the whole text, the header's bytes included
+                                _lib.check(lib.besst_ctx_sam_expect_text(self.ctx._ctx, int(total - text_at)), 'sam_expect_text')
+                        take = held if eof else last_end
+                        if take == 0 and held >= chunk:
+                            raise self._long_line(text_at, chunk)
+                        if take:
+                            info = self._push(main.cuda_stream, t_buf[slot].data_ptr(), take, text_at)
+                            if info[2] >= 0:
+                                rel = int(info[2]) - text_at
+                                words = self._cut(main, t_buf[slot], held, False, rel, status)
+                                raise _sam_error(self.path, info, lines_before + int(self.ingest.records) + int(words[2]) + 1, True)
+                    carry = held - take
+                    if carry:
+                        t_buf[1 - slot][:carry].copy_(t_buf[slot][take:held])
+                    text_at, slot = text_at + take, 1 - slot
+                    if chain_end and tail:
+                        break
+                self.ingest.inflated_bytes = text_at
+                if tail:                                         # the rest of the file through zlib on the host
+                    stats['host_from'] = int(end)
+                    prefix = t_buf[slot][:carry].cpu().numpy().tobytes()
+                    del t_buf, ws, w_dev
+                    fh.seek(end)
+                    self._read_members(device, device_index, fh, end, prefix, header, in_header, text_at, chunk)
+                elif self.ctx is None:
+                    self._open_context(device, device_index, header)     # a file of header lines alone
+        finally:
+            copy.synchronize()
+            main.synchronize()                                   # nothing is in flight when the buffers are let go, error or not
+
+    def _cut(self, main, text, n_bytes, want_header_end, count_upto, status):
+        """besst_dev_sam_lines over text[:n_bytes] -> the five words of ``status`` on the host: the round's one wait"""
+        import ctypes as C
+        _lib.check(self._lib.besst_dev_sam_lines(C.c_void_p(main.cuda_stream), C.c_void_p(text.data_ptr()), int(n_bytes),
+                                                 1 if want_header_end else 0, int(count_upto), C.c_void_p(status.data_ptr())),
+                   'besst_dev_sam_lines')
+        return status.cpu().tolist()
+
+    def _long_line(self, at, chunk):
+        return SamError('%s: the line at byte %d of the inflated text is longer than chunk_bytes = %d; raise chunk_bytes'
+                        % (self.path, at, chunk), at, None, 'line longer than a chunk')
+
+    def _host_round(self, torch, dev, taken, text):
+        """The blocks of a round inflated by zlib and laid where the device would have put them."""
+        with open(self.path, 'rb') as fh:
+            for tab, a, b, place in taken:
+                parts = []
+                for k in range(a, b):
+                    fh.seek(int(tab['payload_at'][k]))
+                    at = int(tab['starts'][k])
+                    try:
+                        raw = zlib.decompress(fh.read(int(tab['src_len'][k])), -15)
+                    except zlib.error as exc:
+                        raise self._compressed_error('the BGZF block at byte %d of the compressed SAM file does not inflate: %s'
+                                                     % (at, exc), at)
+                    if len(raw) != int(tab['isize'][k]) or (zlib.crc32(raw) & 0xffffffff) != int(tab['crc'][k]):
+                        raise self._compressed_error('the BGZF block at byte %d of the compressed SAM file is damaged: its '
+                                                     'inflated bytes are not those of its CRC-32 and ISIZE' % at, at)
+                    parts.append(raw)
+                raw = b''.join(parts)
+                if raw:
+                    text[place:place + len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+        torch.cuda.current_stream(dev).synchronize()
+
+    # ---- gzip with gzip_on_gpu: the text is inflated into HBM whole and parsed in place -----------------------------------
+    def _parse_resident(self, device, device_index, torch, dev, text, n):
+        with torch.cuda.device(dev):
             # the header is fetched back from the front of the text
             header, h_bytes, window, done = [], 0, 1 << 20, False
             while not done and h_bytes < n:
@@ -419,9 +699,6 @@ class ResidentSam(object):
                     window *= 4                                  # a header line longer than the window
             self._open_context(device, device_index, header)
             body = n - h_bytes
-            if body > SAM_MAX_TEXT:
-                raise MemoryError('%s: %d bytes of inflated record text; a compressed SAM is parsed as one chunk of less than '
-                                  '4 GiB - inflate the file first, a plain SAM file is streamed in chunks' % (self.path, body))
             if body == 0:
                 return
             if h_bytes % 16:                                     # the parser wants its text 16-byte aligned: the records move
@@ -461,6 +738,55 @@ class ResidentSam(object):
     def close(self):
         if self.ctx is not None:
             self.ctx.close()
+
+
+def _split_lines(data):
+    """bytes -> its lines with their '\\n' (only '\\n' ends a line); a last line without one is a line"""
+    lines = data.split(b'\n')
+    last = lines.pop()
+    return [line + b'\n' for line in lines] + ([last] if last else [])
+
+
+class _MemberStream(object):
+    """``readinto`` over the inflated bytes of the gzip members of an open file (GenerateOutput._gzip_members: zlib on the
+    host, a piece at a time) behind ``prefix``, for ResidentSam._stream_lines; ``header_lines`` takes the leading '@' lines."""
+
+    def __init__(self, fh, base=0, prefix=b''):
+        from . import GenerateOutput as GO
+        self._pieces = GO._gzip_members(fh, base=base)
+        self._buf, self._at = bytes(prefix), 0
+
+    def _more(self):
+        while self._at >= len(self._buf):
+            piece = next(self._pieces, None)
+            if piece is None:
+                return False
+            self._buf, self._at = piece, 0
+        return True
+
+    def readinto(self, view):
+        got = 0
+        while got < len(view) and self._more():
+            k = min(len(view) - got, len(self._buf) - self._at)
+            view[got:got + k] = memoryview(self._buf)[self._at:self._at + k]
+            got, self._at = got + k, self._at + k
+        return got
+
+    def header_lines(self):
+        """-> (the leading run of '@' lines, their bytes); the stream stands behind them"""
+        lines, size = [], 0
+        while self._more() and self._buf[self._at] == 64:
+            parts = []
+            while self._more():
+                nl = self._buf.find(b'\n', self._at)
+                stop = len(self._buf) if nl < 0 else nl + 1
+                parts.append(self._buf[self._at:stop])
+                self._at = stop
+                if nl >= 0:
+                    break
+            lines.append(b''.join(parts))
+            size += len(lines[-1])
+        return lines, size
 
 
 def _read_full(fh, view):

@@ -74,7 +74,8 @@ def build_parser():
     ap.add_argument('-c', dest='contigfile', required=True,
                     help='contig FASTA, plain or gzip / BGZF compressed (told by its first bytes, not its name)')
     ap.add_argument('-f', dest='bamfiles', nargs='+', required=True,
-                    help='one BAM or SAM file per library (SAM text plain, BGZF or gzip; told by content, not by name)')
+                    help='one BAM or SAM file per library (SAM text plain, BGZF or gzip; told by content, not by name; every form is '
+                         'streamed in chunks, so a compressed SAM may be of any size - BGZF is inflated on the GPU)')
     ap.add_argument('-o', dest='output', default='.', help='output directory')
     ap.add_argument('-orientation', dest='orientation', nargs='+', choices=['fr', 'rf'], required=True)
     ap.add_argument('-r', dest='readlen', type=int, nargs='+')

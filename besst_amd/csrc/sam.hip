@@ -21,11 +21,16 @@
 // No pass walks SEQ, QUAL or the optional fields a byte per lane, a line may span any number of tiles, and no order
 // depends on an atomic: a record's row is its line's rank.  Errors are a status: the smallest offending file offset (the
 // line's first byte) with the line's reason code below it in one word, by 64-bit atomicMin.
+//
+// The line cutter (besst_dev_sam_lines) serves a reader that fills a buffer with inflated text and has to know where its
+// last whole line ends without fetching the text: one pass of the same 16-byte loads and newline masks, a wave per run of
+// rounds, the rule of a slice in sam_lines_core.h; a wave reduces by shuffles and adds at most one atomic per answer.
 #include <vector>
 
 #include "common.h"
 #include "context.h"
 #include "sam_core.h"
+#include "sam_lines_core.h"
 
 namespace besst {
 
@@ -290,6 +295,48 @@ __global__ __launch_bounds__(kSamDecodeThreads) void sam_decode_kernel(const uin
     if (m != 0ull && (threadIdx.x & 63) == 0) atomicAdd(saturated, (unsigned long long)__popcll(m));
 }
 
+// ---- the line cutter: where the last line ends, where the header ends, the newlines in front of a byte -----------------
+constexpr int kLinesMaxBlocks = 2048;                            // waves enough for every CU; a wave's run of rounds grows behind that
+
+__global__ __launch_bounds__(kSamThreads) void sam_lines_kernel(const uint8_t* __restrict__ text, int64_t n, int64_t count_upto,
+                                                                int want_header_end, int64_t n_rounds, int64_t per_wave,
+                                                                unsigned long long* __restrict__ out) {
+    namespace L = besst_sam_lines;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kSamWaves + (threadIdx.x >> 6);
+    const int64_t r0 = wave * per_wave;
+    const int64_t r1 = r0 + per_wave < n_rounds ? r0 + per_wave : n_rounds;
+    if (r0 >= r1) return;
+    bool prev_nl = nl_before(text, r0 * kSamRound);
+    L::Acc a = L::acc_none();
+    for (int64_t r = r0; r < r1; ++r) {
+        const int64_t off = r * kSamRound + lane * 16;
+        L::Slice s{0u, 0u, 0u};
+        if (off < n) {
+            const sam_u32x4 v = *reinterpret_cast<const sam_u32x4*>(text + off);     // at most 15 bytes past the end: the pad
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            s = L::slice_masks(w, n - off);
+        }
+        const int up = __shfl_up((int)(s.nl >> 15), 1);
+        const uint32_t before = lane == 0 ? (uint32_t)prev_nl : (uint32_t)up;
+        prev_nl = __shfl((int)(s.nl >> 15), 63) != 0;
+        if (off < n) L::acc_slice(a, s, before, off, n, count_upto, want_header_end != 0);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        L::Acc b;
+        b.last_end = (uint32_t)__shfl_xor((int)a.last_end, d);
+        b.first_rec = (uint32_t)__shfl_xor((int)a.first_rec, d);
+        b.newlines = (uint32_t)__shfl_xor((int)a.newlines, d);
+        L::acc_join(a, b);
+    }
+    if (lane == 0) {
+        if (a.last_end) atomicMax(out, (unsigned long long)a.last_end);
+        if (a.first_rec != L::kNone) atomicMin(out + 1, (unsigned long long)a.first_rec);
+        if (a.newlines) atomicAdd(out + 2, (unsigned long long)a.newlines);
+    }
+}
+
 struct SamPlan {
     int rounds;
     int64_t n_tiles;
@@ -365,6 +412,27 @@ extern "C" {
 size_t besst_dev_sam_workspace_bytes(int64_t text_bytes, int64_t tile_bytes) {
     SamPlan p;
     return plan_sam(text_bytes, tile_bytes, &p) ? p.bytes : 0;
+}
+
+int besst_dev_sam_lines(void* stream, const uint8_t* text, int64_t n_bytes, int32_t want_header_end, int64_t count_upto,
+                        int64_t* out) {
+    BESST_REQUIRE(out && (text || n_bytes == 0), "sam_lines: null pointer");
+    BESST_REQUIRE(n_bytes >= 0 && n_bytes < ((int64_t)1 << 32) - 16, "sam_lines: n_bytes must lie in 0..2^32-17");
+    BESST_REQUIRE((reinterpret_cast<uintptr_t>(text) & 15) == 0, "sam_lines: text must be 16-byte aligned");
+    BESST_REQUIRE(count_upto >= 0 && count_upto <= n_bytes, "sam_lines: count_upto must lie in 0..n_bytes");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    BESST_HIP_TRY(hipMemsetAsync(out, 0, 32, s));
+    BESST_HIP_TRY(hipMemsetAsync(out + 1, 0xff, 8, s));           // no such line start: -1
+    if (n_bytes == 0) return BESST_OK;
+    const int64_t n_rounds = (n_bytes + kSamRound - 1) / kSamRound;
+    const int64_t max_waves = (int64_t)kLinesMaxBlocks * kSamWaves;
+    const int64_t per_wave = (n_rounds + max_waves - 1) / max_waves;
+    const int64_t waves = (n_rounds + per_wave - 1) / per_wave;
+    hipLaunchKernelGGL(sam_lines_kernel, dim3((uint32_t)((waves + kSamWaves - 1) / kSamWaves)), dim3(kSamThreads), 0, s, text,
+                       n_bytes, count_upto, (int)want_header_end, n_rounds, per_wave,
+                       reinterpret_cast<unsigned long long*>(out));
+    BESST_HIP_TRY(hipGetLastError());
+    return BESST_OK;
 }
 
 int besst_ctx_set_sam_references(besst_ctx* c, const uint8_t* names, const int64_t* name_off, int64_t n_ref) {

@@ -49,7 +49,8 @@ extern "C" {
  * with the trailing member besst_lib_params.tid_bits (see there); the candidate side stream besst_cand_stream with
  * besst_dev_candidate_offsets_bytes / besst_dev_candidate_stream_bytes / besst_dev_candidate_offsets /
  * besst_dev_candidate_stream, the trailing member besst_lib_params.cand_stream, and besst_dev_record_loop_form; the layout
- * a device ingest leaves beside the columns: besst_ctx_layout_state / besst_ctx_fetch_layout. */
+ * a device ingest leaves beside the columns: besst_ctx_layout_state / besst_ctx_fetch_layout; the line cutter of a
+ * streamed compressed SAM besst_dev_sam_lines. */
 #define BESST_ABI_VERSION 3
 
 /* status codes */
@@ -1202,7 +1203,21 @@ int besst_bgzf_deflate_device(int device, const void* src, size_t n_bytes, int32
  *   besst_ctx_sam_pass_times       measurement (tools/time_sam_ingest.py): ms[0..4), where given, receives the device time
  *                                  of the flags, state, index (with the rows' memset) and decode passes summed over the
  *                                  pushes since the last call, by events; the sums are cleared and the events switched on
- *                                  or off for the pushes that follow. */
+ *                                  or off for the pushes that follow.
+ *   besst_dev_sam_lines            the line cutter of a reader that fills a device buffer with inflated text (a compressed
+ *                                  SAM, bamio.ResidentSam): one pass over text[0, n_bytes) - 16-byte aligned, n_bytes below
+ *                                  2^32 - 16, 16 readable bytes behind the end, bytes behind n_bytes masked as the parser
+ *                                  masks them - enqueued on `stream` leaves in out (device, four words)
+ *                                    out[0] the offset behind the last '\n' of the text (0: none)
+ *                                    out[1] with want_header_end != 0, the smallest line start whose byte is not '@'; a
+ *                                           line start is byte 0 and every byte behind a '\n' that lies inside the text.
+ *                                           -1: none (and without want_header_end, and for an empty text); n_bytes: every
+ *                                           line is a header line and the last one is complete
+ *                                    out[2] the number of '\n' in text[0, count_upto)
+ *                                    out[3] 0
+ *                                  A wave reduces by shuffles and adds at most one 64-bit atomic per word.  BESST_ERR_ARG
+ *                                  without touching the device: a null pointer, a misaligned text, n_bytes or count_upto
+ *                                  (0..n_bytes) out of range. */
 #define BESST_SAM_INFO_WORDS 4
 #define BESST_SAM_FEW_FIELDS 1
 #define BESST_SAM_EMPTY_LINE 2
@@ -1222,6 +1237,8 @@ int besst_ctx_push_sam_text(besst_ctx* ctx, void* stream, const uint8_t* text, i
                             uint16_t* head_qlen, int64_t* info);
 int besst_ctx_sam_expect_text(besst_ctx* ctx, int64_t text_bytes);
 int besst_ctx_sam_pass_times(besst_ctx* ctx, int enable, double* ms);
+int besst_dev_sam_lines(void* stream, const uint8_t* text, int64_t n_bytes, int32_t want_header_end, int64_t count_upto,
+                        int64_t* out);
 
 #ifdef __cplusplus
 }
