@@ -532,7 +532,7 @@ size_t metrics_workspace_bytes(int64_t n) {
 }
 
 // Scan records [start, start+count).  state: 6 x int64 on the device (see layout above); state[0..2] are exact up to the
-// cut-offs and at least the cut-off beyond them (a part that begins with both lists full is not looked at).
+// cut-offs and at least the cut-off beyond them (a part that begins with both lists full - an insert-size list that is not asked for counts as full - is not looked at: state[0..2] stay as they were).
 // count_only: only the three running counts (state[0..2]) advance - the first phase of a sharded scan, whose
 // slices need the counts of the slices before them to place their samples.
 int launch_metrics(hipStream_t s, const MetricsArgs& a, int64_t start, int64_t count, int32_t* isize_out,
