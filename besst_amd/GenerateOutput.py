@@ -342,6 +342,11 @@ class SequenceStore(object):
     def byte_at(self, pool_offset):
         return int(self._pool[EMIT_PAD + int(pool_offset)].item())
 
+    def report(self, rows=None, min_gap=1):
+        """The census of the contigs (seqreport.census_store): bases by class, lower case, runs of 'N', per row."""
+        from . import seqreport
+        return seqreport.census_store(self, rows, min_gap)
+
     def close(self):
         self._pool = self._off = self._len = self._names = self._name_off = None
         self.pool_ptr = None
@@ -956,6 +961,7 @@ class ScaffoldLayout(object):
         out_off = np.zeros(n_rows + 1, dtype=np.int64)
         np.cumsum(length, out=out_off[1:])
         self.drop, self.body_rows = drop, pre + 1
+        self.header_rows, self.newline_rows = pre[self.first], np.flatnonzero(is_nl)
         return dict(src_off=src, len=length, mode=mode, out_off=out_off, literals=literals,
                     total=int(out_off[-1]), merges=[(int(c), int(drop[c])) for c in np.flatnonzero(drop > 0)])
 
@@ -1058,9 +1064,26 @@ class ScaffoldEmitter(object):
             p(self._len.data_ptr()), p(self._mode.data_ptr()), p(self._out_off.data_ptr()), int(begin), int(end),
             p(out.data_ptr()), p(self._err.data_ptr() + 16)), 'besst_dev_emit_scaffolds')
 
-    def check(self):
+    def sequence_ranges(self):
+        """Where every scaffold's sequence lies in the FASTA, from the piece table -> (offsets, lengths) int64, in the order
+        of ``layout.names``: behind its header line, up to its '\\n'."""
+        out_off, lay = self.table['out_off'], self.layout
+        begin = out_off[lay.header_rows + 1]
+        return begin, out_off[lay.newline_rows] - begin
+
+    def report(self, window_bytes=None, min_gap=1):
+        """The census of the scaffolds AS EMITTED (seqreport.census_source over this emitter's bytes): reversal, merged
+        overlaps, the single 'n' joins and the 'N' fills are counted exactly as they are written -> SequenceCensus
+        (partial) named by ``layout.names``.  Raises what ``check`` raises; the `merging` lines are not printed again."""
+        from . import seqreport
+        src = ByteSource(self.torch, self.dev, self.total, self.emit, lambda: self.check(quiet=True))
+        seq_off, seq_len = self.sequence_ranges()
+        words = seqreport.census_source(src, seq_off, seq_len, window_bytes, min_gap)
+        return seqreport.SequenceCensus(self.layout.names, words, min_gap)
+
+    def check(self, quiet=False):
         """After the last range: the `merging` lines the reference prints up to its first KeyError go to
-        ``param.information_file``, then that error is raised."""
+        ``param.information_file`` (``quiet``: they do not), then that error is raised."""
         self.torch.cuda.synchronize(self.dev)
         err = self._err.cpu().numpy().view(np.uint64)
         if int(err[3]) != NO_ERROR:
@@ -1068,7 +1091,7 @@ class ScaffoldEmitter(object):
         hit = self.layout.locate(int(err[2]), int(err[0]))
         error = None if hit is None else KeyError(chr(self.store.byte_at(hit[1])))
         for c, n in self.table['merges']:
-            if hit is None or c < hit[0]:
+            if not quiet and (hit is None or c < hit[0]):
                 print('merging {0} bp here'.format(n), file=self.param.information_file)
         if error is not None:
             raise error
@@ -1441,6 +1464,11 @@ def PrintOutput(F, Information, output_dest, param, pass_nr, store=None, unique_
                 _write_agp_gff(em.layout, agp, gff)
             if getattr(param, 'outputs_on_gpu', False):
                 split = dict(text='host')
+        if getattr(param, 'assembly_report', False):
+            from . import seqreport
+            t_report = time.time()
+            seqreport.write_pass_report(em, Information, pass_dir, param)
+            split['assembly_report'] = time.time() - t_report
         last_timings.clear()
         last_timings.update(em.seconds, emit_kernels=spent['emit_kernels'], bgzf_kernels=spent['bgzf_kernels'],
                             d2h=spent['d2h'], file_write=spent['file_write'], fasta_file_bytes=spent['file_bytes'],

@@ -151,7 +151,11 @@ _SIGNATURES = {
     'besst_dev_library_report_words': (C.c_int64, [C.c_int64, C.c_int64]),
     'besst_dev_library_report': (C.c_int, [_P, C.POINTER(ReportArgs), _P]),
     'besst_ctx_library_report': (C.c_int, [_P, C.c_int64, _P, C.c_int64]),
-    'besst_ctx_value_histogram': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    'besst_dev_seq_census_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
+    'besst_dev_seq_census_tile_bytes': (C.c_int64, []),
+    'besst_dev_seq_census': (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),
+    'besst_host_seq_census': (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
+    'besst_ctx_value_histogram':(C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
     'besst_ctx_build_graph': (C.c_int, [_P]),
     'besst_ctx_edge_count': (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'besst_ctx_fetch_edges': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),

@@ -21,7 +21,10 @@ scaffold FASTA is compressed on the GPU and written as ``Scaffolds-pass<n>.fa.gz
 ``Scaffolds_pass<n>.fa.gz``, the repeats appended as further BGZF blocks.  AGP, GFF, ``repeats.fa``,
 ``low_coverage_contigs.fa`` and the TSVs stay plain.  With ``--bam_report`` every pass also counts what its BAM holds, in
 one pass over the resident records on the GPU, and writes ``pass<n>/bam_report.tsv``, ``idxstats.tsv``, ``mapq_hist.tsv``,
-``qlen_hist.tsv`` and ``insert_sizes.tsv`` (besst_amd.report).  BESST's path
+``qlen_hist.tsv`` and ``insert_sizes.tsv`` (besst_amd.report).  With ``--assembly_report`` the contigs are counted on the
+GPU before pass 1 - bases by class, lower case, runs of N: ``contig_report.tsv`` - and with ``--scaffolds`` every pass
+writes ``pass<n>/scaffold_report.tsv`` for its scaffolds as written and ``pass<n>/assembly_stats.tsv`` (N50 / L50, gaps, GC:
+contigs beside scaffolds; ``--report_min_gap N``: a run of N counts as a gap from N bases on; besst_amd.seqreport).  BESST's path
 search (PROWithinScaf / PROBetweenScaf) stays with BESST - see INTEGRATION.md for plugging these calls into runBESST.
 
 Several GPUs of one node: launch the same command line under torchrun, one process per GPU -
@@ -43,7 +46,7 @@ from time import time
 from . import CreateGraph as CG
 from . import GenerateOutput as GO
 from . import MakeScaffolds as MS
-from . import Parameter, bamio, libmetrics, mathstats_compat, report, session
+from . import Parameter, bamio, libmetrics, mathstats_compat, report, seqreport, session
 
 
 def open_fasta(path):
@@ -126,6 +129,14 @@ def build_parser():
                          'idxstats.tsv (the numbers of samtools idxstats), mapq_hist.tsv, qlen_hist.tsv and insert_sizes.tsv; '
                          'the census goes to Statistics.txt too, with a note when the pairs speak against -orientation or '
                          "the contig lengths against the header's")
+    ap.add_argument('--assembly_report', dest='assembly_report', action='store_true',
+                    help='count what the contigs hold on the GPU - bases by class, lower case, runs of N - and write '
+                         'contig_report.tsv, one row per contig, before pass 1; with --scaffolds every pass also writes '
+                         'pass<n>/scaffold_report.tsv for its scaffolds as written and pass<n>/assembly_stats.tsv (N50 / L50, '
+                         'N90 / L90, auN, GC, gaps: contigs beside scaffolds), and the before -> after lines go to '
+                         'Statistics.txt.  Contigs that hold a byte the scaffold writer has no complement for are named')
+    ap.add_argument('--report_min_gap', dest='report_min_gap', type=int, default=1, metavar='N',
+                    help='with --assembly_report: a run of N counts as a gap from this many bases on (default 1)')
     ap.add_argument('--linearize', action='store_true',
                     help="also run steps 1-4 of MakeScaffolds.Algorithm on a copy of G (isolated scaffolds, "
                          "score-based ambiguity removal, cycles) and write the surviving link edges")
@@ -186,6 +197,28 @@ def write_scaffolds(G, G_prime, Contigs, small_contigs, Scaffolds, small_scaffol
     GO.PrintOutput(F, Information, param.output_directory, param, pass_nr, store=store)
     print('Time elapsed for writing the scaffolds, iteration ' + str(pass_nr - 1) + ': ' + str(time() - t0) + '\n',
           file=Information)
+
+
+def write_contig_report(store, C_dict, param, out, Information, min_gap, per_pass):
+    """--assembly_report, before pass 1: the census of the run's contigs (the rows of the filtered ``C_dict``) from the
+    store as BESST_output/contig_report.tsv, the baseline column of every pass's assembly_stats.tsv, and one warning line -
+    stderr and Statistics.txt - that names up to ten contigs holding a byte the scaffold writer has no complement for."""
+    t0 = time()
+    census = store.report(rows=[store.index[name] for name in C_dict], min_gap=min_gap).finalised()
+    census.write(os.path.join(out, 'contig_report.tsv'))
+    param.contig_stats = stats = seqreport.AssemblyStats(census)
+    param.report_min_gap = min_gap
+    param.assembly_report = per_pass                              # PrintOutput writes the per-pass files
+    print('Assembly report of the contigs (contig_report.tsv): %d sequences, %d bases, N50 %s, L50 %s, %d gaps, %d N, '
+          'counted in %s s' % (stats.n, stats.total, stats.N50, stats.L50, stats.gaps, stats.n_bases, time() - t0),
+          file=Information)
+    odd = [name for name, other in zip(census.names, census.other.tolist()) if other > 0]
+    if odd:
+        line = ('WARNING: %d contig(s) hold a byte that is no base, N or IUPAC code (%s%s): a pass that writes one of them '
+                'reversed stops with the KeyError of that byte, as BESST does' % (
+                    len(odd), ', '.join(odd[:10]), ', ...' if len(odd) > 10 else ''))
+        print(line, file=sys.stderr)
+        print(line, file=Information)
 
 
 def write_bam_report(records, param, C_dict, pass_dir, Information, lead):
@@ -341,9 +374,11 @@ def _run(args, rank):
     Contigs, Scaffolds, small_contigs, small_scaffolds = {}, {}, {}, {}
     if not fasta_on_gpu:
         # the sequences go to the GPU once, before CreateGraph.PE drops repeats and low-coverage contigs from its dicts
-        store = GO.SequenceStore(list(C_dict), list(C_dict.values())) if args.scaffolds and lead else None
+        store = GO.SequenceStore(list(C_dict), list(C_dict.values())) if (args.scaffolds or args.assembly_report) and lead else None
         if store is not None and args.outputs_on_gpu:
             store.batch_fasta = True
+    if args.assembly_report and lead:
+        write_contig_report(store, C_dict, param, out, Information, args.report_min_gap, bool(args.scaffolds))
     for i, bam in enumerate(args.bamfiles):
         param.pass_number = i + 1
         param.bamfile = bam

@@ -1240,6 +1240,68 @@ int besst_ctx_sam_pass_times(besst_ctx* ctx, int enable, double* ms);
 int besst_dev_sam_lines(void* stream, const uint8_t* text, int64_t n_bytes, int32_t want_header_end, int64_t count_upto,
                         int64_t* out);
 
+/* ---- the sequence census: what a byte string holds, counted where it lies (csrc/seq_census.hip, seq_census_core.h) ------
+ * The census of one byte string is BESST_CENSUS_WORDS words of int64:
+ *   LEN        bytes seen
+ *   A C G T    counts, case folded
+ *   N          'N' or 'n'
+ *   IUPAC      YRKMBVHDSW in either case, and upper-case X
+ *   OTHER      every other byte value: the bytes besst_host_complement_table has no complement for, so OTHER > 0 says that
+ *              writing the string reversed raises the reference's KeyError
+ *   LOWER      bytes 'a'..'z', whatever their class
+ *   PRE        length of the run of N that starts at byte 0 (LEN if the string is all N)
+ *   SUF        length of the run of N that ends at the last byte (LEN if all N)
+ *   RUNS       closed runs of N: those that touch neither end
+ *   GAPS       ... of length >= min_gap;  GAP_BASES: the sum of their lengths;  LONGEST: the longest closed run
+ *   word 15    0
+ * Merge of neighbours a·b (census_merge): an empty side yields the other; words 0-8, RUNS, GAPS and GAP_BASES add, LONGEST
+ * is the maximum; PRE = a is all N ? a.LEN + b.PRE : a.PRE; SUF = b is all N ? a.SUF + b.LEN : b.SUF; if neither side is
+ * all N and a.SUF + b.PRE > 0 that joined run is closed.  The rule is associative, so a string may be counted in pieces
+ * of any size.  Finalise (census_finalise, the caller's, after the last merge): an all-N string closes one run of LEN,
+ * otherwise PRE and SUF are each closed if they are not zero.
+ *
+ * besst_dev_seq_census: buf[0 .. n) is a window of a longer byte stream and begins at stream position `origin`; row i of
+ * the table is the stream bytes [seq_off[i], seq_off[i] + seq_len[i]), rows ascending and disjoint (rows of length 0
+ * anywhere).  For every row that intersects the window the call counts the intersection and merges it into acc as the
+ * right-hand neighbour, acc[i] = merge(acc[i], part); rows that do not intersect keep their words bit for bit.  The caller
+ * zeroes acc before the first window and hands the windows of a stream over in ascending order on one stream.  The rows
+ * are found by a search of the window's bounds in seq_off: the work is that of the window, whatever n_seq is.
+ *   Reads: only aligned 16-byte groups that hold a byte of the window (any address of buf; a buffer that is readable in
+ *   whole 16-byte groups - the sequence pool with its BESST_EMIT_PAD, an output buffer of whole groups - satisfies it).
+ *   workspace: besst_dev_seq_census_workspace_bytes(n, n_seq) bytes for windows of up to n bytes, 16-byte aligned;
+ *   the tile partials of the rows that cross a border of besst_dev_seq_census_tile_bytes() bytes live there.
+ *   status[0]: min over the rows the call walked (every row from the one the search finds to the first one behind the
+ *   window, each held against its predecessor) of the rows that begin in front of their predecessor's end or have a
+ *   negative field; the caller sets both words to -1 (all ones) before the first window.  Such a table makes the
+ *   result meaningless, never a read or a write outside the buffers.  status[1]: min over the walked rows of those with
+ *   a negative offset or length (they are counted as empty), -1 if there is none.
+ *   Nothing is allocated, nothing waits.  n == 0 or n_seq == 0: nothing is launched.
+ * besst_host_seq_census: the same on host memory with the same rules, byte by byte (BESST_ERR_ARG and the row in
+ * besst_last_error for a table that is out of order). */
+#define BESST_CENSUS_WORDS 16
+#define BESST_CENSUS_LEN 0
+#define BESST_CENSUS_A 1
+#define BESST_CENSUS_C 2
+#define BESST_CENSUS_G 3
+#define BESST_CENSUS_T 4
+#define BESST_CENSUS_N 5
+#define BESST_CENSUS_IUPAC 6
+#define BESST_CENSUS_OTHER 7
+#define BESST_CENSUS_LOWER 8
+#define BESST_CENSUS_PRE 9
+#define BESST_CENSUS_SUF 10
+#define BESST_CENSUS_RUNS 11
+#define BESST_CENSUS_GAPS 12
+#define BESST_CENSUS_GAP_BASES 13
+#define BESST_CENSUS_LONGEST 14
+#define BESST_CENSUS_TILE_BYTES 8192
+size_t besst_dev_seq_census_workspace_bytes(int64_t window_bytes, int64_t n_seq);
+int64_t besst_dev_seq_census_tile_bytes(void);
+int besst_dev_seq_census(void* stream, const uint8_t* buf, int64_t origin, int64_t n, int64_t n_seq, const int64_t* seq_off,
+                         const int64_t* seq_len, int64_t min_gap, void* workspace, int64_t* acc, int64_t* status);
+int besst_host_seq_census(const uint8_t* buf, int64_t origin, int64_t n, int64_t n_seq, const int64_t* seq_off,
+                          const int64_t* seq_len, int64_t min_gap, int64_t* acc);
+
 #ifdef __cplusplus
 }
 #endif
