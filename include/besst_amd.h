@@ -932,6 +932,18 @@ size_t besst_dev_exchange_region_bytes(int64_t pair_capacity);
  * rider_bytes = 0: no rider, stride = region. */
 size_t besst_dev_exchange_stride_bytes(int64_t pair_capacity, int64_t rider_bytes);
 uint32_t besst_owner_of_scaffold(uint32_t scaffold_id, uint32_t world);
+/* What the two calls define, word by word (tests/exchange_design.py holds both against a byte-for-byte model):
+ *   besst_dev_partition writes, per region, header words 0..3 = { tuples sent = min(wanted, pair_capacity), tuples
+ *   wanted, min(*n_tuples, capacity), 0 }, words 4..11 ONLY where slice_info is given, words 12 and 13 ONLY where
+ *   slice_info[7] names a tuple of the stream (0 <= slice_info[7] < min(*n_tuples, capacity); 13 may be at or beyond
+ *   pair_capacity when the owner's region overflowed), the first `sent` entries of the three columns and the rider.
+ *   Words 14 and 15, words 4..13 in the other cases and the column slots behind `sent` keep whatever the buffer held.
+ *   besst_dev_unpack writes keys / payload / gidx up to *n_out and nothing behind it; it only ever SETS *overflow (the
+ *   caller clears it before the call); with speculative heads the counter corrections are added to `counters` when
+ *   rider_bytes is 0 and to the last eight words of rider_sum otherwise (`counters` is then left alone, but must still be
+ *   given; rider_bytes 8..56 is refused); all_slice_info is written only with speculative heads.
+ *   Both return an error before any launch for a world outside [1, 256], a pair_capacity that is not positive (partition:
+ *   and even), a rider that is not a multiple of 8 bytes, and - unpack, speculative heads - a rank outside the world. */
 /* workspace: besst_dev_reduce_workspace_bytes(capacity) */
 int besst_dev_partition(void* stream, int64_t capacity, const uint32_t* n_tuples, int32_t node_bits,
                         int32_t world, const uint64_t* keys, const uint64_t* payload, int64_t pair_capacity,
